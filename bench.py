@@ -16,6 +16,10 @@ the file's page table lives on the GPU and each call's bytes land in that stream
 ``ring[stream, call]`` — no call is skipped or merged.  depth defaults to 1 MiB of calls per
 stream (256 for 4 KiB), the amortisation the reference client gets from 1 MiB chunk buffers.
 
+A plain run sets up, warms up, times the ``--steps`` steps of the ``local`` phase, checks sampled
+ring slots against the file, writes its outputs if ``--dump-outputs DIR`` is given and prints the
+result line.  Every other phase runs only with ``--full`` (``--phases`` then selects among them).
+
 Phases (all timed between a barrier + ``torch.cuda.synchronize()`` on both sides; max over ranks):
 
 * ``local``  (the headline ``value``): every stream starts at offset 0, as StressWorkerBench's
@@ -34,8 +38,15 @@ Phases (all timed between a barrier + ``torch.cuda.synchronize()`` on both sides
 ``value`` = total bytes read by all ranks in the K timed ``local`` steps / max-over-ranks time
 (GB/s, whole node, weak scaling: each worker serves its own file).
 
-Run: python bench.py [--gpus N --steps K --warmup W].  With N > 1 and no torchrun environment
-the script launches ``torch.distributed.run`` itself as a child process (before touching the GPU).
+``--dump-outputs DIR`` writes what the last timed ``local`` step delivered, as float32/float64
+``.npy`` files: ``ring.npy`` holds a fixed, seeded sample of ring slots (one row per sampled
+``read(buf)`` call, bytes past the call's length zeroed) and ``calls.npy`` one row
+``(stream, call, file offset, length)`` per sampled slot.  The file bytes are seeded, so two runs
+with the same arguments write the same arrays.  With N > 1 ranks, rank r > 0 writes
+``ring.rank<r>.npy`` / ``calls.rank<r>.npy``.
+
+Run: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  With N > 1
+and no torchrun environment the script launches ``torch.distributed.run`` itself as a child process (before touching the GPU).
 """
 import argparse
 import json
@@ -64,7 +75,12 @@ def parse_args(argv=None):
     ap.add_argument("--page-size", default="2m")
     ap.add_argument("--depth", type=int, default=0,
                     help="read calls per stream per step (0 = 1 MiB of calls per stream)")
-    ap.add_argument("--phases", default=",".join(PHASES), help="comma list of " + "/".join(PHASES))
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary phases (everything but local); off by default")
+    ap.add_argument("--phases", default=",".join(PHASES),
+                    help="comma list of " + "/".join(PHASES) + "; phases other than local need --full")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write a seeded sample of the last timed local step's ring slots to DIR/*.npy")
     ap.add_argument("--duration", type=float, default=2.0, help="seconds for the duration phase")
     ap.add_argument("--phase-timeout", type=float, default=180.0,
                     help="deadline (s) of the cross-rank remote/replicate phases; past it the run "
@@ -112,6 +128,8 @@ def main(argv=None):
     for p in phases:
         if p not in PHASES:
             raise SystemExit(f"unknown phase {p}")
+    if not a.full:
+        phases = ["local"]
 
     import numpy as np
     import torch
@@ -285,12 +303,34 @@ def main(argv=None):
         barrier()
         return el, nb
 
+    DUMP_ELEMS = 8 << 20      # sampled ring bytes per rank: 32 MB as float32
+
+    def dump_outputs(reader, ring):
+        """What the last step delivered: a fixed, seeded sample of (stream, call) ring slots."""
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        width = min(buf, DUMP_ELEMS)
+        nslots = max(1, min(a.threads * depth, DUMP_ELEMS // width))
+        slots = np.sort(np.random.default_rng(20240).choice(a.threads * depth, nslots, replace=False))
+        rows = np.zeros((nslots, width), dtype=np.float32)
+        calls = np.zeros((nslots, 4), dtype=np.float64)
+        for i, slot in enumerate(slots):
+            s, k = divmod(int(slot), depth)
+            off, n = reader.last_call(s, k)
+            calls[i] = (s, k, off, n)
+            n = min(n, width)
+            rows[i, :n] = ring[s, k, :n].cpu().numpy()
+        tag = f".rank{rank}" if rank else ""
+        np.save(os.path.join(a.dump_outputs, f"ring{tag}.npy"), rows)
+        np.save(os.path.join(a.dump_outputs, f"calls{tag}.npy"), calls)
+
     def run_phase(name, make_reader, ring, src, steps, warmup):
         nonlocal ok_all
         reader = make_reader(ring)
         try:
             el, nb = timed(reader, steps, warmup)
             good = verify(reader, ring, src)
+            if name == "local" and a.dump_outputs:
+                dump_outputs(reader, ring)
         finally:
             reader.close()
         el_max, total = MAX(el), SUM(float(nb))
@@ -319,6 +359,7 @@ def main(argv=None):
             "reader": "gpu-consumer (same-GPU device ring), device-cursor ring x%d, streams start at offset 0" % depth,
             "verified": bool(ok_all),
             "headline_verified": bool(local["verified"]),
+            "full": bool(a.full),
             "phase_errors": phase_errors or None,
             "stagger_GBps": results.get("stagger", {}).get("GBps"),
             "host_reader_GBps": results.get("host", {}).get("GBps"),

@@ -1,4 +1,5 @@
-"""bench.py contract: --gpus N launches N ranks itself, every phase verifies its bytes.
+"""bench.py contract: --gpus N launches N ranks itself, every phase verifies its bytes; a plain
+run times only the headline phase, --full adds the secondary ones.
 
 Runs on CPU with the gloo backend and shared-memory DRAM arenas: the ``remote`` phase maps the
 peer worker's arena (memfd) exactly as the GPU path maps a peer's HBM (HIP IPC), and the
@@ -25,8 +26,36 @@ def _run(args, tmp_path, expect_rc=0, extra_env=None):
     return json.loads(lines[0])
 
 
-SMALL = ["--steps", "3", "--warmup", "1", "--file-size", "8m", "--block-size", "4m", "--page-size", "1m",
-         "--threads", "8", "--duration", "0.2"]
+PLAIN = ["--steps", "3", "--warmup", "1", "--file-size", "8m", "--block-size", "4m", "--page-size", "1m",
+         "--threads", "8"]
+SMALL = [*PLAIN, "--duration", "0.2", "--full"]
+
+
+def test_bench_plain_run_times_only_the_headline_and_dumps_its_outputs(tmp_path):
+    """Without --full only the local phase runs (even when --phases names others), and
+    --dump-outputs writes the sampled ring slots of the last timed step: float32 rows that equal
+    the seeded file bytes at each sampled call's offset, identical from run to run."""
+    import numpy as np
+    outs = []
+    for name in ("a", "b"):
+        work = tmp_path / name
+        work.mkdir()
+        out = _run([*PLAIN, "--phases", "local,stagger,duration", "--dump-outputs", str(work / "dump")], work)
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["config"]["headline_verified"]
+        assert list(out["config"]["phases"]) == ["local"]
+        # 3 timed steps x 8 streams x 256 calls of 4 KiB
+        assert out["config"]["phases"]["local"]["bytes"] == 3 * 8 * 256 * 4096
+        assert sorted(os.listdir(work / "dump")) == ["calls.npy", "ring.npy"]
+        outs.append((np.load(work / "dump" / "ring.npy"), np.load(work / "dump" / "calls.npy")))
+    (ring, calls), (ring_b, calls_b) = outs
+    assert ring.dtype == np.float32 and calls.dtype == np.float64
+    assert ring.shape == (8 * 256, 4096) and calls.shape == (8 * 256, 4)
+    assert np.array_equal(ring, ring_b) and np.array_equal(calls, calls_b)
+    data = np.random.default_rng(1234).integers(0, 256, 8 << 20, dtype=np.uint8)
+    # the last of 4 steps: every stream's 256 calls cover the fourth MiB of the file
+    assert np.array_equal(calls[:, 2], np.tile(np.arange(256) * 4096.0 + (3 << 20), 8))
+    assert np.all(calls[:, 3] == 4096)
+    assert np.array_equal(ring, np.tile(data[3 << 20:4 << 20].reshape(256, 4096), (8, 1)).astype(np.float32))
 
 
 def test_bench_single_rank(tmp_path):

@@ -553,7 +553,8 @@ sys.path.insert(0, %(root)r)
 import torch
 from alluxio_amd.ops.native import lib
 handle, offset, nbytes, probes = bytes.fromhex(%(handle)r), %(offset)d, %(nbytes)d, %(probes)r
-base = lib().ipc_open_bounded(handle, 0, %(timeout_ms)d) + offset
+mapped = lib().ipc_open_bounded(handle, 0, %(timeout_ms)d)
+base = mapped + offset
 out = {}
 for off in probes:                       # read 4 KiB at each probe, write its complement back
     dst = torch.empty(4096, dtype=torch.uint8, device="cuda")
@@ -563,6 +564,11 @@ for off in probes:                       # read 4 KiB at each probe, write its c
     inv = (255 - dst).contiguous()
     lib().batched_copy([(inv.data_ptr(), base + off, 4096)], 0)
 torch.cuda.synchronize()
+# close the mapping before exiting: the exporter frees the arena as soon as this process has ended,
+# and an import that is only torn down with the process can outlive that free by a moment -- an
+# allocation that then reuses the arena's address range cannot be exported (hipIpcGetMemHandle:
+# invalid argument), which made the 6 GiB case fail from time to time after the 3 GiB one
+lib().ipc_close(mapped)
 print(json.dumps({str(k): v for k, v in out.items()}), flush=True)
 """
 

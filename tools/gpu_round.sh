@@ -31,7 +31,7 @@ for s in $STEPS; do
   case $s in
     tests) run pytest_gpu 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.build(); g.smoke()" ;;
-    bench) run bench_default 400 python bench.py ;;
+    bench) run bench_default 400 python bench.py --full ;;
     bench20) run bench_driver 300 python bench.py --gpus 1 --steps 20 --warmup 5 ;;
     variants)
       run bench_buf4m 300 python bench.py --buffer-size 4m --steps 200 --warmup 20
@@ -113,12 +113,12 @@ for s in $STEPS; do
     pmcdram)
       # HBM bytes behind the lockstep (local) and staggered readers, one counter pass each
       run pmc_dram_local 240 rocprofv3 --pmc TCC_EA0_RDREQ_DRAM_sum TCC_EA0_WRREQ_DRAM_sum --kernel-trace --stats -d "$OUT/pmc_dram_local" -o pmc --output-format csv -- python3 bench.py --steps 20 --warmup 2 --phases local
-      run pmc_dram_stagger 240 rocprofv3 --pmc TCC_EA0_RDREQ_DRAM_sum TCC_EA0_WRREQ_DRAM_sum --kernel-trace --stats -d "$OUT/pmc_dram_stagger" -o pmc --output-format csv -- python3 bench.py --steps 20 --warmup 2 --phases local,stagger
+      run pmc_dram_stagger 240 rocprofv3 --pmc TCC_EA0_RDREQ_DRAM_sum TCC_EA0_WRREQ_DRAM_sum --kernel-trace --stats -d "$OUT/pmc_dram_stagger" -o pmc --output-format csv -- python3 bench.py --full --steps 20 --warmup 2 --phases local,stagger
       ;;
     large)
       # the HBM-resident read rate: 16 GiB file, staggered streams (DRAM read bytes ~= delivered)
-      run bench_large 400 python bench.py --steps 20 --warmup 5 --phases local,stagger,large
-      run pmc_dram_large 300 rocprofv3 --pmc TCC_EA0_RDREQ_DRAM_sum TCC_EA0_WRREQ_DRAM_sum --kernel-trace --stats -d "$OUT/pmc_dram_large" -o pmc --output-format csv -- python3 bench.py --steps 20 --warmup 2 --phases local,large
+      run bench_large 400 python bench.py --full --steps 20 --warmup 5 --phases local,stagger,large
+      run pmc_dram_large 300 rocprofv3 --pmc TCC_EA0_RDREQ_DRAM_sum TCC_EA0_WRREQ_DRAM_sum --kernel-trace --stats -d "$OUT/pmc_dram_large" -o pmc --output-format csv -- python3 bench.py --full --steps 20 --warmup 2 --phases local,large
       ;;
     k9put)
       run pytest_pc 300 python -u -m pytest tests/test_page_cache_native.py -x -v --timeout 120 --timeout-method thread
@@ -167,8 +167,8 @@ for s in $STEPS; do
       run worker_write_bench_grpcio 600 python tools/worker_write_bench.py --threads 1,4,16 --file-size 256m --transports grpc --client-prop alluxio.user.native.writer.enabled=false --out "$OUT/worker_write_bench_grpcio.jsonl"
       ;;
     rehearse)
-      run bench_rehearse_2rank 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --one-device --steps 10 --warmup 3
-      run bench_rehearse_4rank 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 4 --one-device --steps 10 --warmup 3
+      run bench_rehearse_2rank 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --one-device --steps 10 --warmup 3
+      run bench_rehearse_4rank 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29518 bench.py --full --gpus 4 --one-device --steps 10 --warmup 3
       ;;
     lz4encprof)
       run rocprof_lz4enc 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_lz4enc" -o lz4enc --output-format csv -- python3 tools/lz4_bench.py --chunks 1024 --variants=-1
@@ -231,25 +231,25 @@ for s in $STEPS; do
       run ww_mc_final 600 python tools/worker_write_bench.py --threads 1,4,8,16 --file-size 256m --write-type MUST_CACHE --out "$OUT/r5_worker_write_cache_through_final.jsonl"
       ;;
     arenaab)
-      run bench_arena_native_a 400 python bench.py
+      run bench_arena_native_a 400 python bench.py --full
       export ALLUXIO_HBM_ARENA_TORCH=1
-      run bench_arena_torch_a 400 python bench.py
-      run rocprof_arena_torch 500 rocprofv3 --kernel-trace --stats -d "$OUT/prof_arena_torch" -o bench --output-format csv -- python3 bench.py --steps 50 --warmup 5
+      run bench_arena_torch_a 400 python bench.py --full
+      run rocprof_arena_torch 500 rocprofv3 --kernel-trace --stats -d "$OUT/prof_arena_torch" -o bench --output-format csv -- python3 bench.py --full --steps 50 --warmup 5
       unset ALLUXIO_HBM_ARENA_TORCH
-      run rocprof_arena_native 500 rocprofv3 --kernel-trace --stats -d "$OUT/prof_arena_native" -o bench --output-format csv -- python3 bench.py --steps 50 --warmup 5
-      run bench_arena_native_b 400 python bench.py
+      run rocprof_arena_native 500 rocprofv3 --kernel-trace --stats -d "$OUT/prof_arena_native" -o bench --output-format csv -- python3 bench.py --full --steps 50 --warmup 5
+      run bench_arena_native_b 400 python bench.py --full
       export ALLUXIO_HBM_ARENA_TORCH=1
-      run bench_arena_torch_b 400 python bench.py
+      run bench_arena_torch_b 400 python bench.py --full
       unset ALLUXIO_HBM_ARENA_TORCH
       ;;
     batchab)
-      run bench_batch_default 400 python bench.py --phases local,duration
+      run bench_batch_default 400 python bench.py --full --phases local,duration
       export DEBUG_CLR_MAX_BATCH_SIZE=4096
-      run bench_batch_4096 400 python bench.py --phases local,duration
-      run rocprof_batch_4096 500 rocprofv3 --kernel-trace --stats -d "$OUT/prof_batch_4096" -o bench --output-format csv -- python3 bench.py --phases local,duration --duration 1
+      run bench_batch_4096 400 python bench.py --full --phases local,duration
+      run rocprof_batch_4096 500 rocprofv3 --kernel-trace --stats -d "$OUT/prof_batch_4096" -o bench --output-format csv -- python3 bench.py --full --phases local,duration --duration 1
       unset DEBUG_CLR_MAX_BATCH_SIZE
       export DEBUG_CLR_BATCH_CPU_SYNC_SIZE=4096
-      run bench_cpusync_4096 400 python bench.py --phases local,duration
+      run bench_cpusync_4096 400 python bench.py --full --phases local,duration
       unset DEBUG_CLR_BATCH_CPU_SYNC_SIZE
       ;;
     ctrep)
@@ -280,9 +280,9 @@ for s in $STEPS; do
       done
       ;;
     r6large)
-      run bench_large_r6 400 python bench.py --steps 20 --warmup 5 --phases local,stagger,large
+      run bench_large_r6 400 python bench.py --full --steps 20 --warmup 5 --phases local,stagger,large
       run copy_roof_r6 300 python tools/copy_roof.py --gib 4 --out "$OUT/r6_copy_roof.json"
-      run pmc_dram_large_r6 300 rocprofv3 --pmc TCC_EA0_RDREQ_DRAM_sum TCC_EA0_WRREQ_DRAM_sum --kernel-trace --stats -d "$OUT/pmc_dram_large_r6" -o pmc --output-format csv -- python3 bench.py --steps 20 --warmup 2 --phases local,large
+      run pmc_dram_large_r6 300 rocprofv3 --pmc TCC_EA0_RDREQ_DRAM_sum TCC_EA0_WRREQ_DRAM_sum --kernel-trace --stats -d "$OUT/pmc_dram_large_r6" -o pmc --output-format csv -- python3 bench.py --full --steps 20 --warmup 2 --phases local,large
       ;;
     r6w8s)
       # sustained 8 s writes, 64 MiB blocks (the round-6 commit target rows)
@@ -402,11 +402,11 @@ for s in $STEPS; do
         run cold_final_p$par 300 python tools/remote_device_read_bench.py --uds --cold --dest host --file-size 2g --read-size 2g --native-only --client-prop alluxio.user.device.read.parallelism=$par --out "$OUT/r6_final_cold.jsonl"
         run cached_final_p$par 300 python tools/remote_device_read_bench.py --uds --dest host --file-size 2g --read-size 2g --native-only --client-prop alluxio.user.device.read.parallelism=$par --out "$OUT/r6_final_cold.jsonl"
       done
-      run fanout_final 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29523 bench.py --gpus 8 --one-device --steps 10 --warmup 3 --phases local,replicate --profile-json "$OUT/r6_final_fanout.json"
+      run fanout_final 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29523 bench.py --full --gpus 8 --one-device --steps 10 --warmup 3 --phases local,replicate --profile-json "$OUT/r6_final_fanout.json"
       ;;
     r6fanout)
       # replica fan-out breakdown: 8 ranks (8 workers) on the one GPU, 3 replicas per block
-      run bench_rehearse_8rank_r6 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 8 --one-device --steps 10 --warmup 3 --phases local,replicate --profile-json "$OUT/r6_rehearse_8rank.json"
+      run bench_rehearse_8rank_r6 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29519 bench.py --full --gpus 8 --one-device --steps 10 --warmup 3 --phases local,replicate --profile-json "$OUT/r6_rehearse_8rank.json"
       ;;
     r6create)
       # temp block created after 2 reads (old) vs after every slot filled once (0), A/B/A/B, same box
@@ -461,7 +461,7 @@ for s in $STEPS; do
     final)
       run pytest_gpu_final 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread
       run smoke_final 300 python -c "import __graft_entry__ as g; g.build(); g.smoke()"
-      run bench_final 400 python bench.py
+      run bench_final 400 python bench.py --full
       run wb_host_sweep_final 900 python tools/worker_bench_host.py --threads 16,64,256 --transports grpc,ipc --duration 6s --warmup 2s --out "$OUT/r5_worker_bench_host_sweep.jsonl"
       ;;
     roof)
