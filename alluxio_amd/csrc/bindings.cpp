@@ -14,6 +14,7 @@
 #include "ipc.h"
 #include "numa_host.h"
 #include "ring_read.h"
+#include "ragged_gather.h"
 #include "kernels.h"
 #include "seg_ring.h"
 #include "frame_rpc.h"
@@ -578,6 +579,61 @@ PYBIND11_MODULE(_C, m) {
       .def_property_readonly("calls", &RingReadSession::calls)
       .def_property_readonly("file_len", &RingReadSession::file_len);
 
+  // ---- device-planned ragged record gather (ragged_gather.cpp) --------------------------------
+  py::class_<RaggedGatherSession>(m, "RaggedGatherSession")
+      .def(py::init([](BlockStore& store, int64_t session,
+                       const std::vector<std::pair<std::vector<int64_t>, std::vector<uint64_t>>>& files,
+                       const std::vector<py::array_t<uint64_t, py::array::c_style | py::array::forcecast>>& offsets) {
+             std::vector<std::vector<uint64_t>> offs;
+             offs.reserve(offsets.size());
+             for (auto& o : offsets) offs.emplace_back(o.data(), o.data() + o.size());
+             py::gil_scoped_release rel;
+             return new RaggedGatherSession(&store, session, files, offs);
+           }),
+           py::arg("store"), py::arg("session"), py::arg("files"), py::arg("offsets"), py::keep_alive<1, 2>())
+      .def_static("raw", [](uint64_t arena, const std::vector<int64_t>& pages, uint64_t page_size, int device,
+                            py::array_t<uint64_t, py::array::c_style | py::array::forcecast> rec_start,
+                            py::array_t<uint32_t, py::array::c_style | py::array::forcecast> rec_len) {
+             std::vector<uint64_t> rs(rec_start.data(), rec_start.data() + rec_start.size());
+             std::vector<uint32_t> rl(rec_len.data(), rec_len.data() + rec_len.size());
+             py::gil_scoped_release rel;
+             return std::unique_ptr<RaggedGatherSession>(
+                 new RaggedGatherSession(arena, pages, page_size, device, rs, rl));
+           },
+           py::arg("arena_base"), py::arg("pages"), py::arg("page_size"), py::arg("device"), py::arg("rec_start"),
+           py::arg("rec_len"))
+      // Returns (bytes of dst the batch occupies, record bytes gathered).  out_off: uint64 [B+1],
+      // out_len: uint32 [B], both in the memory kind of dst.
+      .def("gather",
+           [](RaggedGatherSession& g, py::array_t<int64_t, py::array::c_style | py::array::forcecast> idx,
+              uint64_t dst, uint64_t capacity, uint64_t out_off, uint64_t out_len, const std::string& layout,
+              uint32_t align, uint64_t row_stride, uint32_t max_len, uint32_t pad_value, int dst_kind,
+              uint64_t stream) {
+             RaggedLayout lay;
+             if (layout == "padded") lay.padded = true;
+             else if (layout != "packed") throw StoreError(kErrInvalidArgument, "ragged gather: layout must be packed or padded");
+             lay.align = align;
+             lay.row_stride = row_stride;
+             lay.max_len = max_len;
+             lay.pad_value = pad_value;
+             uint64_t data = 0, total;
+             {
+               py::gil_scoped_release rel;
+               total = g.gather(idx.data(), (uint64_t)idx.size(), dst, capacity, out_off, out_len, lay, dst_kind,
+                                stream, &data);
+             }
+             return py::make_tuple(total, data);
+           },
+           py::arg("idx"), py::arg("dst"), py::arg("capacity"), py::arg("out_off"), py::arg("out_len"),
+           py::arg("layout") = "packed", py::arg("align") = 16, py::arg("row_stride") = 0, py::arg("max_len") = 0,
+           py::arg("pad_value") = 0, py::arg("dst_kind") = 1, py::arg("stream") = 0)
+      .def("close", &RaggedGatherSession::close, G())
+      .def_property_readonly("records", &RaggedGatherSession::records)
+      .def_property_readonly("arena_on_device", &RaggedGatherSession::arena_on_device)
+      .def_property_readonly("gathers", &RaggedGatherSession::gathers)
+      .def_property_readonly_static("max_batch", [](py::object) { return kRaggedGatherMaxBatch; })
+      .def_static("set_index_copy", &RaggedGatherSession::set_index_copy, py::arg("on"));
+
   // ---- native S3 data path (http_blob.cpp) --------------------------------------------------
   py::class_<BlobServer>(m, "BlobServer")
       .def(py::init<const std::string&, const std::string&, int>(), py::arg("root"), py::arg("host") = "127.0.0.1",
@@ -914,6 +970,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("set_lz4_decode_variant", &set_lz4_decode_variant, py::arg("variant"));
   m.def("set_lz4_encode_variant", &set_lz4_encode_variant, py::arg("variant"));
   m.def("set_seq_read_variant", &set_seq_read_variant, py::arg("variant"), py::arg("grid_cap") = 0);
+  m.def("set_ragged_gather_variant", &set_ragged_gather_variant, py::arg("variant"), py::arg("chunk_shift") = 0);
+  m.def("ragged_gather_chunk_shift", &ragged_gather_chunk_shift);
   m.def("set_page_gather_chunk_variant", &set_page_gather_chunk_variant, py::arg("variant"));
   m.attr("COPY_CHUNK") = kCopyChunk;
 }

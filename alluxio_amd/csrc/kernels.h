@@ -59,6 +59,59 @@ hipError_t launch_seq_read(const SeqReadArgs& a, hipStream_t stream);
 // A/B switch for the sequential-read kernel (bit0: nontemporal ring stores, bit1: unroll 16).
 void set_seq_read_variant(int variant, unsigned grid_cap);
 
+// Ragged gather (ragged_gather.hip): `batch` variable-length records, picked by `idx` from a
+// device-resident record index (RaggedRec: virtual byte address and length), are read through a
+// virtual page table (vtab: virtual page -> arena page) into one destination buffer.
+//   packed: row r starts at out_off[r] = previous end rounded up to `align` (a power of two,
+//           1..256); the gap bytes are zero; out_off[batch] is the total.
+//   padded: row r starts at r * row_stride and holds min(len, max_len) bytes followed by
+//           pad_value up to max_len; out_len[r] is the truncated length.
+// Two launches: a one-workgroup plan (lengths, prefix sums of the row offsets and of the work-item
+// counts, in rounds of 4096 rows with a carry) and a copy whose waves grid-stride over work items
+// of 2^chunk_shift 16-byte destination vectors.  The caller validates everything that decides
+// addresses (indices, capacity, record index inside vtab); the launcher re-checks the scalars.
+struct RaggedRow {
+  uint64_t src;       // virtual byte address of the record
+  uint64_t dst_off;   // byte offset of the row in dst
+  uint64_t span;      // bytes of dst the row owns: data, then fill (gap or padding)
+  uint32_t len;       // data bytes (truncated in the padded layout)
+  uint32_t chunk0;    // exclusive prefix of the work-item counts
+};
+struct RaggedRec {      // one 16-byte load per row in the plan
+  uint64_t start;     // virtual byte address
+  uint32_t len;
+  uint32_t pad;
+};
+struct RaggedGatherArgs {
+  const uint8_t* arena;
+  const int64_t* vtab;
+  const RaggedRec* recs;     // [n_rec] record index (device)
+  const int64_t* idx;        // [batch] record numbers (device memory, or pinned host memory the device can read)
+  uint8_t* dst;
+  uint64_t* out_off;         // [batch + 1]
+  uint32_t* out_len;         // [batch]
+  RaggedRow* rows;           // [batch] workspace
+  uint32_t* chunk_pre;       // [batch + 1] workspace
+  uint64_t n_rec;
+  uint64_t row_stride;       // padded
+  uint32_t batch;
+  uint32_t page_shift;
+  uint32_t align;            // packed
+  uint32_t max_len;          // padded
+  uint32_t padded;           // 0 = packed, 1 = padded
+  uint32_t pad_value;
+  uint32_t total_chunks;     // host count of the work items (same formula as the plan)
+  uint32_t chunk_shift;      // log2(16-byte vectors per work item), from ragged_gather_chunk_shift()
+};
+constexpr uint32_t kRaggedGatherMaxBatch = 65536;
+hipError_t launch_ragged_gather(const RaggedGatherArgs& a, hipStream_t stream);
+// Inner loop of the copy: 0 = unaligned 16-byte loads feeding the aligned stores (a vector that
+// straddles a page or a row edge takes the funnel), 1 = aligned loads + a byte funnel over two
+// registers, the second register taken from the next lane.  chunk_shift (0 = keep) sets the
+// work-item size: 2^chunk_shift vectors of 16 bytes per wave.
+void set_ragged_gather_variant(int variant, unsigned chunk_shift);
+uint32_t ragged_gather_chunk_shift();
+
 // CRC32C (Castagnoli, reflected, init/xorout 0xFFFFFFFF) of `n` equal-length pieces
 // (piece i = base + i*piece_bytes, last may be shorter: total_bytes).  `out` device array.
 hipError_t launch_crc32c_pieces(const uint8_t* base, uint64_t total_bytes, uint64_t piece_bytes,

@@ -14,6 +14,13 @@ flight while the model consumes the current one:
 
 ``FixedRecordDataset`` is the map-style view (``torch.utils.data.Dataset``) for code that wants
 per-sample access; ``DeviceBatchLoader`` is the fast path.
+
+Variable-length records (tokenised documents, encoded images) are an ``IndexedRecordDataset``:
+per-file offset arrays (or the ``<path>.idx`` sidecar, or one record per file).  The loader then
+yields ``RaggedBatch(data, offsets, lengths)``, packed or padded.  When one in-process worker holds
+every block in one memory dir, a batch is one ``RaggedGatherSession.gather``: the page table and
+the record index live on the device, a plan launch sizes the rows and a copy launch moves them, and
+the host does nothing per record or page.  Other sources take the general path above.
 """
 from __future__ import annotations
 
@@ -162,13 +169,195 @@ class FileListDataset(FixedRecordDataset):
         return idx, 0
 
 
+INDEX_MAGIC = b"AMDXIDX1"
+
+
+def _check_offsets(offsets, what: str) -> np.ndarray:
+    off = np.asarray(offsets)
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError(f"{what}: a record index is a 1-D array of n+1 offsets")
+    if off.dtype.kind not in "iu":
+        raise ValueError(f"{what}: offsets must be integers")
+    if off.dtype.kind == "u" and off.size and int(off.max()) > np.iinfo(np.int64).max:
+        raise ValueError(f"{what}: offset out of range")
+    off = off.astype(np.int64)
+    if int(off[0]) < 0 or (off.size > 1 and bool((np.diff(off) < 0).any())):
+        raise ValueError(f"{what}: record offsets must be non-negative and must not decrease")
+    return off
+
+
+def write_index(fs, path: str, offsets, **kw) -> str:
+    """Write the sidecar ``<path>.idx`` of a record file: ``AMDXIDX1``, a uint64 ``n`` and the
+    ``n+1`` uint64 record offsets, little-endian.  Returns the sidecar's path."""
+    off = _check_offsets(offsets, path)
+    body = INDEX_MAGIC + np.array([off.size - 1], dtype="<u8").tobytes() + off.astype("<u8").tobytes()
+    fs.write_file(path + ".idx", body, **kw)
+    return path + ".idx"
+
+
+def read_index(fs, path: str) -> np.ndarray:
+    """The int64 offsets stored in ``<path>.idx`` (see :func:`write_index`)."""
+    raw = fs.read_file(path + ".idx")
+    if len(raw) < 16 or raw[:8] != INDEX_MAGIC:
+        raise ValueError(f"{path}.idx: not a record index (bad magic)")
+    n = int(np.frombuffer(raw, dtype="<u8", count=1, offset=8)[0])
+    if len(raw) < 16 + 8 * (n + 1):
+        raise ValueError(f"{path}.idx: truncated ({len(raw)} bytes for {n} records)")
+    return _check_offsets(np.frombuffer(raw, dtype="<u8", count=n + 1, offset=16), path + ".idx")
+
+
+class RaggedBatch(tuple):
+    """``(data, offsets, lengths)`` of a batch of variable-length records.  Packed: ``data`` is
+    1-D and record r is ``data[offsets[r]:offsets[r] + lengths[r]]``; padded: ``data`` is
+    ``[B, max_len]`` and ``offsets[r] = r * max_len``.  Offsets and lengths count elements."""
+
+    __slots__ = ()
+
+    def __new__(cls, data, offsets, lengths):
+        return tuple.__new__(cls, (data, offsets, lengths))
+
+    data = property(lambda self: self[0])
+    offsets = property(lambda self: self[1])
+    lengths = property(lambda self: self[2])
+
+
+class IndexedRecordDataset:
+    """Variable-length records laid end to end in one or more files.  ``index`` holds, per file,
+    the ``n+1`` monotone byte offsets of its records (``None``: read the sidecar ``<path>.idx``)."""
+
+    ragged = True
+
+    def __init__(self, fs, paths, index=None, dtype="uint8", device=None):
+        paths = [paths] if isinstance(paths, str) else list(paths)
+        if index is None:
+            index = [read_index(fs, p) for p in paths]
+        elif len(paths) == 1 and not isinstance(index, (list, tuple)):
+            index = [index]
+        if len(index) != len(paths):
+            raise ValueError("one offset array per file is required")
+        files = [_FileLayout(fs.get_status(p)) for p in paths]
+        self.paths = paths
+        self._init(fs, files, [_check_offsets(o, p) for o, p in zip(index, paths)],
+                   np.array([f.length for f in files], dtype=np.int64), dtype, device)
+
+    def _init(self, fs, files, offsets, file_lengths, dtype, device, file_blocks=None):
+        import torch
+        self.fs = fs
+        self.dtype = getattr(torch, str(dtype)) if isinstance(dtype, str) else dtype
+        self.itemsize = torch.empty(0, dtype=self.dtype).element_size()
+        self.device = device
+        self.files = files
+        self.offsets = offsets
+        self._file_blocks = file_blocks
+        for k, off in enumerate(offsets):
+            if int(off[-1]) > int(file_lengths[k]):
+                raise ValueError(f"file {k}: record offsets run past the end of the file "
+                                 f"({int(off[-1])} > {int(file_lengths[k])})")
+        self.counts = [len(o) - 1 for o in offsets]
+        self.starts = np.cumsum([0] + self.counts)
+        n = int(self.starts[-1])
+        self.record_offsets = np.concatenate([o[:-1] for o in offsets]) if n else np.zeros(0, np.int64)
+        self.lengths = np.concatenate([np.diff(o) for o in offsets]) if n else np.zeros(0, np.int64)
+        if n and int(self.lengths.max()) >= 2 ** 32 - 256:
+            raise ValueError("records of 4 GiB or more are not supported")
+        if self.itemsize > 1 and bool((self.lengths % self.itemsize).any()):
+            raise ValueError(f"every record length must be a multiple of the item size ({self.itemsize})")
+        self.max_bytes = int(self.lengths.max()) if n else 0
+
+    @classmethod
+    def from_files(cls, fs, directory: str, dtype="uint8", device=None):
+        """One record per file of ``directory`` at its true length, from one columnar listing."""
+        self = cls.__new__(cls)
+        cols = fs.list_status_columns(directory) if hasattr(fs, "list_status_columns") else None
+        file_blocks = None
+        if cols is None:
+            sts = sorted((s for s in fs.list_status(directory) if not s.is_folder), key=lambda s: s.path)
+            self.paths = [s.path for s in sts]
+            lengths = np.array([s.length for s in sts], dtype=np.int64)
+            files = [_FileLayout(s) for s in sts]
+        else:
+            keep = np.nonzero(cols.folder == 0)[0]
+            paths = [cols.paths[i] for i in keep]
+            if any(paths[k] > paths[k + 1] for k in range(len(paths) - 1)):
+                order = sorted(range(len(paths)), key=paths.__getitem__)
+                keep, paths = keep[order], [paths[k] for k in order]
+            self.paths = paths
+            lengths = cols.lengths[keep].astype(np.int64)
+            files = _LazyLayouts(cols, keep)
+            if bool(np.all(cols.nblocks[keep] <= 1)):
+                # single-block files: the session's block list comes from the columns alone
+                first = cols.first_blocks[keep].astype(np.int64)
+                file_blocks = [([int(b)], [int(n)]) if n else ([], []) for b, n in zip(first, lengths)]
+        self._init(fs, files, [np.array([0, n], dtype=np.int64) for n in lengths], lengths, dtype, device,
+                   file_blocks)
+        return self
+
+    def __len__(self):
+        return int(self.starts[-1])
+
+    def locate(self, idx: int) -> tuple[int, int]:
+        """(file index, byte offset) of record ``idx``."""
+        if idx < 0:
+            idx += len(self)
+        if not 0 <= idx < len(self):
+            raise IndexError(idx)
+        f = int(np.searchsorted(self.starts, idx, side="right") - 1)
+        return f, int(self.record_offsets[idx])
+
+    def file_blocks(self):
+        """[(block ids, block lengths)] per file, the form a gather session takes."""
+        if self._file_blocks is None:
+            out = []
+            for f in self.files:
+                ids_ = [int(b) for b in f.block_ids]
+                out.append((ids_, [min(f.block_size, f.length - k * f.block_size) for k in range(len(ids_))]))
+            self._file_blocks = out
+        return self._file_blocks
+
+    def __getitem__(self, idx):
+        import torch
+        if idx < 0:
+            idx += len(self)
+        f, off = self.locate(idx)
+        out = torch.empty(int(self.lengths[idx]), dtype=torch.uint8, device=self.device)
+        if out.numel():
+            with self.fs.open_file(self.files[f].path) as s:
+                s.pread(off, out)
+        return out.view(self.dtype)
+
+
 class DeviceBatchLoader:
-    """Iterates ``[batch, *shape]`` device tensors of records gathered by one kernel per batch."""
+    """Iterates ``[batch, *shape]`` device tensors of records gathered by one kernel per batch.
+
+    Over an :class:`IndexedRecordDataset` it yields :class:`RaggedBatch` instead: ``layout`` is
+    ``"packed"`` (row starts rounded up to ``align`` bytes, a power of two up to 256; gaps are
+    zero) or ``"padded"`` (``[B, max_len]`` elements, longer records truncated, the rest filled
+    with the byte ``pad_value``; ``max_len`` defaults to the longest record).  With
+    ``device_plan="auto"`` a batch is one ``RaggedGatherSession.gather`` when every block is held
+    by one in-process worker in one memory dir; ``device_plan=False`` keeps the general path."""
 
     def __init__(self, dataset: FixedRecordDataset, batch_size: int, shuffle: bool = False, seed: int = 0,
-                 drop_last: bool = False, device=None, prefetch: int = 2):
+                 drop_last: bool = False, device=None, prefetch: int = 2, layout: str = "packed", align: int = 16,
+                 max_len: int | None = None, pad_value: int = 0, device_plan="auto"):
         import torch
         self.ds = dataset
+        self.ragged = bool(getattr(dataset, "ragged", False))
+        if self.ragged:
+            if layout not in ("packed", "padded"):
+                raise ValueError("layout must be 'packed' or 'padded'")
+            if align < 1 or align > 256 or align & (align - 1):
+                raise ValueError("align must be a power of two from 1 to 256")
+            if not 0 <= pad_value <= 255:
+                raise ValueError("pad_value is one byte")
+            if device_plan not in ("auto", False):
+                raise ValueError("device_plan must be 'auto' or False")
+            self.layout = layout
+            self.align = max(align, dataset.itemsize)      # rows start on whole elements
+            self.max_bytes = dataset.max_bytes if max_len is None else int(max_len) * dataset.itemsize
+            self.pad_value = pad_value
+        self.device_plan = device_plan
+        self._gather = False          # RaggedGatherSession once opened; None: general path
+        self._gather_worker = None
         self.batch_size = batch_size
         self.shuffle = shuffle
         self.seed = seed
@@ -229,6 +418,10 @@ class DeviceBatchLoader:
 
     def close(self):
         from ..proto import pb
+        if self._gather:
+            self._gather.close()
+        self._gather = False
+        self._gather_worker = None
         for holder, lk in getattr(self, "_locks", []):
             try:
                 if isinstance(lk, int):
@@ -243,11 +436,12 @@ class DeviceBatchLoader:
         self._one_worker = False
 
     # ---- planning -----------------------------------------------------------------------------
-    def _pieces(self, rec_idx: int):
-        """[(block info, offset in block, length, offset in record)] for one record."""
+    def _pieces(self, rec_idx: int, nbytes: int | None = None):
+        """[(block info, offset in block, length, offset in record)] for one record (its first
+        ``nbytes`` bytes; default: the dataset's fixed record size)."""
         f, off = self.ds.locate(rec_idx)
         lay = self.ds.files[f]
-        out, done, n = [], 0, self.ds.record_bytes
+        out, done, n = [], 0, self.ds.record_bytes if nbytes is None else nbytes
         while done < n:
             bi = (off + done) // lay.block_size
             boff = (off + done) - bi * lay.block_size
@@ -284,17 +478,24 @@ class DeviceBatchLoader:
                                        1 if out.is_cuda else 0, stream, not out.is_cuda)
             w._count_read(int(lens.sum()), 1 if out.is_cuda else 0)
             return
-        srcs = self._open_sources()
-        kind = 1 if out.is_cuda else 0
         row = self.ds.record_bytes
+        self._gather_rows(out.view(-1), indices, [r * row for r in range(len(indices))], None)
+
+    def _gather_rows(self, flat, indices, row_offs, lens):
+        """The general path: record ``indices[r]`` (its first ``lens[r]`` bytes; None: the fixed
+        record size) lands at byte ``row_offs[r]`` of the 1-D uint8 tensor ``flat``, planned per
+        record and per block on the host."""
+        srcs = self._open_sources()
+        kind = 1 if flat.is_cuda else 0
         by_worker: dict[int, tuple] = {}
         ipc_segs = []
         slow = []
-        base_ptr = out.data_ptr()
+        base_ptr = flat.data_ptr()
         for r, idx in enumerate(indices):
-            for bi, boff, n, roff in self._pieces(int(idx)):
+            nbytes = None if lens is None else int(lens[r])
+            for bi, boff, n, roff in self._pieces(int(idx), nbytes):
                 how, obj = srcs[bi.blockId]
-                dst = base_ptr + r * row + roff
+                dst = base_ptr + int(row_offs[r]) + roff
                 if how == "local":
                     by_worker.setdefault(id(obj), (obj, []))[1].append((bi.blockId, boff, n, dst, kind))
                 elif how == "ipc":
@@ -305,14 +506,83 @@ class DeviceBatchLoader:
                     slow.append((r, int(idx)))
         stream = int(self.stream.cuda_stream) if self.stream is not None else 0
         for w, reqs in by_worker.values():
-            w.read_batch(reqs, stream, sync=not out.is_cuda)
+            w.read_batch(reqs, stream, sync=not flat.is_cuda)
         if ipc_segs:
             from ..ops.native import lib
             lib().batched_copy(ipc_segs, stream, True)
         for r, idx in sorted(set(slow)):
             f, off = self.ds.locate(idx)
+            n = self.ds.record_bytes if lens is None else int(lens[r])
             with self.ds.fs.open_file(self.ds.files[f].path) as s:
-                s.pread(off, out[r])
+                s.pread(off, flat[int(row_offs[r]):int(row_offs[r]) + n])
+
+    # ---- variable-length records ---------------------------------------------------------------
+    def _gather_session(self):
+        """The RaggedGatherSession of this loader, or None when the general path serves it
+        (``device_plan=False``, blocks held elsewhere, in several dirs or in a file tier, or
+        batches that live in the other kind of memory than the arena)."""
+        if self._gather is not False:
+            return self._gather
+        self._gather = None
+        if self.device_plan is False or len(self.ds) == 0:
+            return None
+        srcs = self._open_sources()
+        ws = {id(o): o for how, o in srcs.values() if how == "local"}
+        if len(ws) != 1 or not all(how == "local" for how, _ in srcs.values()):
+            return None
+        from ..ops.native import lib
+        w = next(iter(ws.values()))
+        try:
+            g = lib().RaggedGatherSession(w.native, self.session, self.ds.file_blocks(),
+                                          [np.ascontiguousarray(o, dtype=np.uint64) for o in self.ds.offsets])
+        except lib().StoreError as e:
+            if len(e.args) >= 1 and e.args[0] == 6:     # invalid argument: a layout the session does not take
+                return None
+            raise
+        if g.arena_on_device != (self.device.type == "cuda"):
+            g.close()
+            return None
+        self._gather, self._gather_worker = g, w
+        return g
+
+    @traced("DeviceBatchLoader.fill_ragged")
+    def _fill_ragged(self, indices) -> RaggedBatch:
+        import torch
+        ix = np.ascontiguousarray(indices, dtype=np.int64)
+        nb, item = len(ix), self.ds.itemsize
+        lens = self.ds.lengths[ix]
+        padded = self.layout == "padded"
+        if padded:
+            lens = np.minimum(lens, self.max_bytes)
+            data = torch.empty((nb, self.max_bytes), dtype=torch.uint8, device=self.device)
+        else:
+            adv = (lens + (self.align - 1)) & ~np.int64(self.align - 1)
+            data = torch.empty(int(adv.sum()), dtype=torch.uint8, device=self.device)
+        g = self._gather_session()
+        if g is not None:
+            off = torch.empty(nb + 1, dtype=torch.int64, device=self.device)
+            ln32 = torch.empty(nb, dtype=torch.int32, device=self.device)
+            kind = 1 if data.is_cuda else 0
+            stream = int(self.stream.cuda_stream) if self.stream is not None else 0
+            from ..ops.native import native_errors
+            with native_errors():
+                _, nbytes = g.gather(ix, data.data_ptr(), data.numel(), off.data_ptr(), ln32.data_ptr(), self.layout,
+                                     self.align, self.max_bytes, self.max_bytes, self.pad_value, kind, stream)
+            self._gather_worker._count_read(int(nbytes), kind)
+            ln = ln32.to(torch.int64)
+        else:
+            if padded:
+                offs = np.arange(nb + 1, dtype=np.int64) * self.max_bytes
+                data.fill_(self.pad_value)
+            else:
+                offs = np.concatenate([[0], np.cumsum(adv)]).astype(np.int64)
+                data.zero_()
+            self._gather_rows(data.view(-1), ix, offs, lens)
+            off = torch.from_numpy(offs).to(self.device)
+            ln = torch.from_numpy(np.ascontiguousarray(lens, dtype=np.int64)).to(self.device)
+        if item > 1:
+            off, ln = off // item, ln // item
+        return RaggedBatch(data.view(self.ds.dtype), off, ln)
 
     # ---- iteration ----------------------------------------------------------------------------
     def __len__(self):
@@ -330,6 +600,14 @@ class DeviceBatchLoader:
         pending = []
 
         def launch(ix):
+            if self.ragged:
+                if self.stream is None:
+                    return self._fill_ragged(ix), None
+                with torch.cuda.stream(self.stream):
+                    batch = self._fill_ragged(ix)
+                    ev = torch.cuda.Event()
+                    ev.record(self.stream)
+                return batch, ev
             buf = torch.empty((len(ix), self.ds.record_bytes), dtype=torch.uint8, device=self.device)
             if self.stream is not None:
                 with torch.cuda.stream(self.stream):
@@ -351,6 +629,14 @@ class DeviceBatchLoader:
             nxt = next(it, None)
             if nxt is not None:
                 pending.append(launch(nxt))
+            if self.ragged:
+                if ev is not None:
+                    cur = torch.cuda.current_stream(self.device)
+                    cur.wait_event(ev)
+                    for t in buf:
+                        t.record_stream(cur)
+                yield buf
+                continue
             if ev is not None:
                 torch.cuda.current_stream(self.device).wait_event(ev)
                 buf.record_stream(torch.cuda.current_stream(self.device))
