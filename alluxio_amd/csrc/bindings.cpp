@@ -15,6 +15,7 @@
 #include "numa_host.h"
 #include "ring_read.h"
 #include "ragged_gather.h"
+#include "delim_index.h"
 #include "kernels.h"
 #include "seg_ring.h"
 #include "frame_rpc.h"
@@ -41,6 +42,13 @@ struct DevBuf {
   explicit DevBuf(size_t n) { HIP_CHECK(hipMalloc(&p, n ? n : 1)); }
   ~DevBuf() { if (p) (void)hipFree(p); }
 };
+
+// The vector becomes the numpy array's storage (no copy).
+py::array_t<uint64_t> vector_to_array(std::vector<uint64_t>&& v) {
+  auto* keep = new std::vector<uint64_t>(std::move(v));
+  py::capsule owner(keep, [](void* p) { delete static_cast<std::vector<uint64_t>*>(p); });
+  return py::array_t<uint64_t>({(py::ssize_t)keep->size()}, {(py::ssize_t)sizeof(uint64_t)}, keep->data(), owner);
+}
 
 int hip_device_count() {
   int n = 0;
@@ -634,6 +642,37 @@ PYBIND11_MODULE(_C, m) {
       .def_property_readonly_static("max_batch", [](py::object) { return kRaggedGatherMaxBatch; })
       .def_static("set_index_copy", &RaggedGatherSession::set_index_copy, py::arg("on"));
 
+  // ---- record index of a delimited text file (delim_index.cpp) -------------------------------
+  // Both return the uint64 cut positions (the byte after each delimiter), ascending.
+  m.def("delim_index_store",
+        [](BlockStore& store, int64_t session, const std::vector<int64_t>& ids, const std::vector<uint64_t>& lens,
+           uint32_t delimiter) {
+          std::vector<uint64_t> r;
+          {
+            py::gil_scoped_release rel;
+            r = delim_index_store(&store, session, ids, lens, delimiter);
+          }
+          return vector_to_array(std::move(r));
+        },
+        py::arg("store"), py::arg("session"), py::arg("block_ids"), py::arg("block_lengths"), py::arg("delimiter"));
+  // times=True: (cuts, (count_ms, scan_ms, emit_ms)) with the device time of the three launches.
+  m.def("delim_index_raw",
+        [](uint64_t arena, const std::vector<int64_t>& pages, uint64_t page_size, int device, uint64_t vstart,
+           uint64_t bytes, uint32_t delimiter, uint64_t add, bool times) -> py::object {
+          std::vector<uint64_t> r;
+          DelimIndexTimes t;
+          {
+            py::gil_scoped_release rel;
+            r = delim_index_raw(arena, pages, page_size, device, vstart, bytes, delimiter, add, times ? &t : nullptr);
+          }
+          py::object cuts = vector_to_array(std::move(r));
+          if (!times) return cuts;
+          return py::make_tuple(cuts, py::make_tuple(t.count_ms, t.scan_ms, t.emit_ms));
+        },
+        py::arg("arena_base"), py::arg("pages"), py::arg("page_size"), py::arg("device"), py::arg("vstart"),
+        py::arg("bytes"), py::arg("delimiter"), py::arg("add") = 0, py::arg("times") = false);
+  m.def("delim_index_launches", &delim_index_launches);
+
   // ---- native S3 data path (http_blob.cpp) --------------------------------------------------
   py::class_<BlobServer>(m, "BlobServer")
       .def(py::init<const std::string&, const std::string&, int>(), py::arg("root"), py::arg("host") = "127.0.0.1",
@@ -972,6 +1011,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("set_seq_read_variant", &set_seq_read_variant, py::arg("variant"), py::arg("grid_cap") = 0);
   m.def("set_ragged_gather_variant", &set_ragged_gather_variant, py::arg("variant"), py::arg("chunk_shift") = 0);
   m.def("ragged_gather_chunk_shift", &ragged_gather_chunk_shift);
+  m.def("set_delim_index_variant", &set_delim_index_variant, py::arg("variant"), py::arg("tile_shift") = 0);
+  m.def("delim_index_tile_shift", &delim_index_tile_shift);
+  m.def("delim_index_variant", &delim_index_variant);
   m.def("set_page_gather_chunk_variant", &set_page_gather_chunk_variant, py::arg("variant"));
   m.attr("COPY_CHUNK") = kCopyChunk;
 }

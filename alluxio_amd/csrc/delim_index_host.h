@@ -1,0 +1,31 @@
+// Host form of the delimiter index (see DelimIndexArgs in kernels.h): a memchr loop per page of a
+// virtual byte range behind a page table.  No HIP include, so a stand-alone program can compile it.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+namespace amdx {
+
+// Appends add + (offset in the range) + 1 for every byte of [vstart, vstart + bytes) that equals
+// `delim`, ascending.  The caller has checked that the range lies inside vtab.
+inline void delim_index_host(const uint8_t* arena, const int64_t* vtab, uint32_t page_shift, uint64_t vstart,
+                             uint64_t bytes, uint8_t delim, uint64_t add, std::vector<uint64_t>* out) {
+  const uint64_t psize = 1ull << page_shift, pmask = psize - 1;
+  uint64_t done = 0;
+  while (done < bytes) {
+    const uint64_t va = vstart + done, po = va & pmask;
+    const uint64_t take = std::min(bytes - done, psize - po);
+    const uint8_t* p = arena + ((uint64_t)vtab[va >> page_shift] << page_shift) + po;
+    const uint8_t* e = p + take;
+    for (const uint8_t* q = p; q < e; ++q) {
+      q = static_cast<const uint8_t*>(std::memchr(q, delim, (size_t)(e - q)));
+      if (!q) break;
+      out->push_back(add + done + (uint64_t)(q - p) + 1);
+    }
+    done += take;
+  }
+}
+
+}  // namespace amdx

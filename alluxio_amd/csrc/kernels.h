@@ -112,6 +112,41 @@ hipError_t launch_ragged_gather(const RaggedGatherArgs& a, hipStream_t stream);
 void set_ragged_gather_variant(int variant, unsigned chunk_shift);
 uint32_t ragged_gather_chunk_shift();
 
+// Delimiter index (delim_index.hip): the cut positions of a delimited text range.  The virtual
+// byte range [vstart, vstart + bytes) is read through a virtual page table (vtab: virtual page ->
+// arena page, as in the ragged gather); for every byte equal to `delim`, in ascending order,
+//   out[k] = add + (offset of the byte in the range) + 1.
+// Three launches in stream order: count (one wave per tile of 2^tile_shift bytes -> tile_count),
+// scan (one workgroup, exclusive prefix -> tile_base, tile_base[ntiles] = total) and emit (each
+// wave re-reads its tile and writes its cuts from tile_base[t] on; no atomics, so two runs give
+// the same array).  Between scan and emit the caller reads the total and sizes `out`; emit never
+// writes at or past out_cap and its launcher refuses total > out_cap.  The caller validates that
+// the range lies inside vtab and that no page is negative; the launchers re-check the scalars.
+struct DelimIndexArgs {
+  const uint8_t* arena;     // 16-byte aligned
+  const int64_t* vtab;      // device
+  uint32_t* tile_count;     // [ntiles] workspace
+  uint64_t* tile_base;      // [ntiles + 1] workspace
+  uint64_t* out;            // [out_cap] (emit only)
+  uint64_t out_cap;
+  uint64_t vstart;
+  uint64_t bytes;           // > 0
+  uint64_t add;
+  uint32_t ntiles;          // delim_index_tiles(vstart, bytes, tile_shift)
+  uint32_t page_shift;
+  uint32_t tile_shift;      // from delim_index_tile_shift()
+  uint32_t delim;           // one byte
+};
+uint64_t delim_index_tiles(uint64_t vstart, uint64_t bytes, uint32_t tile_shift);
+hipError_t launch_delim_count(const DelimIndexArgs& a, hipStream_t stream);
+hipError_t launch_delim_scan(const DelimIndexArgs& a, hipStream_t stream);
+hipError_t launch_delim_emit(const DelimIndexArgs& a, uint64_t total, hipStream_t stream);
+// variant: 0 = plain loads, 1 (default) = nontemporal loads.  tile_shift (0 = keep; 10..24) sets the bytes
+// one wave owns.
+void set_delim_index_variant(int variant, unsigned tile_shift);
+uint32_t delim_index_tile_shift();
+int delim_index_variant();
+
 // CRC32C (Castagnoli, reflected, init/xorout 0xFFFFFFFF) of `n` equal-length pieces
 // (piece i = base + i*piece_bytes, last may be shorter: total_bytes).  `out` device array.
 hipError_t launch_crc32c_pieces(const uint8_t* base, uint64_t total_bytes, uint64_t piece_bytes,

@@ -2,4 +2,4 @@
 it serves are training / inference input pipelines).  ``dataset`` gathers HBM-cached records
 into device batches with one kernel launch per batch."""
 from .dataset import (DeviceBatchLoader, FixedRecordDataset, IndexedRecordDataset, RaggedBatch,  # noqa: F401
-                      read_index, write_index)
+                      build_delimited_index, read_index, write_index)

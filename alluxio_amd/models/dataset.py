@@ -206,6 +206,86 @@ def read_index(fs, path: str) -> np.ndarray:
     return _check_offsets(np.frombuffer(raw, dtype="<u8", count=n + 1, offset=16), path + ".idx")
 
 
+def _delimiter_byte(delimiter) -> int:
+    d = delimiter.encode() if isinstance(delimiter, str) else bytes(delimiter)
+    if len(d) != 1:
+        raise ValueError(f"the delimiter must be exactly one byte, got {len(d)}")
+    return d[0]
+
+
+def _store_cuts(fs, lay: _FileLayout, delim: int):
+    """Cut positions of one file from the worker's own memory (``delim_index_store``: kernels for
+    an HBM dir, the host loop for a DRAM dir), or None when the loader's rule sends the file to
+    the stream path: a block not held by one in-process worker, or a layout the native call
+    refuses (file tier, several dirs)."""
+    from ..ops.native import lib
+    ctx = getattr(fs, "ctx", None)
+    if ctx is None or not hasattr(ctx, "in_process_worker"):
+        return None
+    holders = None
+    for b in lay.blocks:
+        here = {id(w): w for w in (ctx.in_process_worker(loc.workerAddress) for loc in b.locations) if w is not None}
+        holders = here if holders is None else {k: w for k, w in holders.items() if k in here}
+        if not holders:
+            return None
+    w = next(iter(holders.values()))
+    ids_ = [int(b) for b in lay.block_ids]
+    lens = [min(lay.block_size, lay.length - k * lay.block_size) for k in range(len(ids_))]
+    try:
+        return lib().delim_index_store(w.native, ids.create_session_id(), ids_, lens, delim)
+    except lib().StoreError as e:
+        if len(e.args) >= 1 and e.args[0] in (1, 6):     # block gone or a layout the call does not take
+            return None
+        from ..ops.native import translate
+        raise translate(e) from None
+
+
+def _stream_cuts(fs, path: str, delim: int, chunk_bytes: int) -> np.ndarray:
+    """The same cut positions from the client stream, ``chunk_bytes`` at a time."""
+    parts, pos = [], 0
+    buf = np.empty(max(1, int(chunk_bytes)), dtype=np.uint8)
+    with fs.open_file(path) as f:
+        while True:
+            n = f.readinto(buf)
+            if n <= 0:
+                break
+            parts.append(np.flatnonzero(buf[:n] == delim).astype(np.uint64) + np.uint64(pos + 1))
+            pos += n
+    return np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint64)
+
+
+def build_delimited_index(fs, path: str, delimiter=b"\n", write: bool = False, device_plan="auto",
+                          chunk_bytes: int = 8 << 20, **write_kw) -> np.ndarray:
+    """The record index of a delimited text file (JSONL, CSV, one document per line): int64 offsets
+    ``[0, every cut ..., file length]`` where a cut is the byte after a delimiter, so records keep
+    their trailing delimiter (``bytes.splitlines(keepends=True)`` for ``\\n``), a last line without
+    one is a record and an empty file gives ``[0]``.
+
+    When one in-process worker holds every block in one memory dir the delimiters are found where
+    the bytes are (count, scan and emit kernels through the page table for an HBM dir, a memchr
+    loop for a DRAM dir); otherwise, or with ``device_plan=False``, the file is read through the
+    client stream ``chunk_bytes`` at a time.  All paths return the same array.  ``write=True`` also
+    stores it as the ``<path>.idx`` sidecar (``write_kw`` goes to :func:`write_index`)."""
+    delim = _delimiter_byte(delimiter)
+    if device_plan not in ("auto", False):
+        raise ValueError("device_plan must be 'auto' or False")
+    lay = _FileLayout(fs.get_status(path))
+    cuts = None
+    if device_plan == "auto" and lay.length and len(lay.block_ids):
+        cuts = _store_cuts(fs, lay, delim)
+    if cuts is None:
+        cuts = _stream_cuts(fs, path, delim, chunk_bytes) if lay.length else np.zeros(0, dtype=np.uint64)
+    off = np.empty(cuts.size + 2, dtype=np.int64)
+    off[0] = 0
+    off[1:-1] = cuts
+    off[-1] = lay.length
+    if lay.length == 0 or (cuts.size and int(cuts[-1]) == lay.length):
+        off = off[:-1]
+    if write:
+        write_index(fs, path, off, **write_kw)
+    return off
+
+
 class RaggedBatch(tuple):
     """``(data, offsets, lengths)`` of a batch of variable-length records.  Packed: ``data`` is
     1-D and record r is ``data[offsets[r]:offsets[r] + lengths[r]]``; padded: ``data`` is
@@ -291,6 +371,15 @@ class IndexedRecordDataset:
         self._init(fs, files, [np.array([0, n], dtype=np.int64) for n in lengths], lengths, dtype, device,
                    file_blocks)
         return self
+
+    @classmethod
+    def from_delimited(cls, fs, paths, delimiter=b"\n", dtype="uint8", device=None, write_index: bool = False):
+        """One record per line (or per ``delimiter``-terminated piece) of one or more text files:
+        the index of each file comes from :func:`build_delimited_index`, and ``write_index=True``
+        also stores it as the file's ``.idx`` sidecar."""
+        paths = [paths] if isinstance(paths, str) else list(paths)
+        index = [build_delimited_index(fs, p, delimiter, write=write_index) for p in paths]
+        return cls(fs, paths, index=index, dtype=dtype, device=device)
 
     def __len__(self):
         return int(self.starts[-1])
