@@ -643,34 +643,38 @@ PYBIND11_MODULE(_C, m) {
       .def_static("set_index_copy", &RaggedGatherSession::set_index_copy, py::arg("on"));
 
   // ---- record index of a delimited text file (delim_index.cpp) -------------------------------
-  // Both return the uint64 cut positions (the byte after each delimiter), ascending.
+  // Both return the uint64 cut positions (the byte after each delimiter), ascending.  quote >= 0:
+  // that byte toggles "inside quotes" and a delimiter inside is no cut; in_quote: the state at vstart.
   m.def("delim_index_store",
         [](BlockStore& store, int64_t session, const std::vector<int64_t>& ids, const std::vector<uint64_t>& lens,
-           uint32_t delimiter) {
+           uint32_t delimiter, int64_t quote) {
           std::vector<uint64_t> r;
           {
             py::gil_scoped_release rel;
-            r = delim_index_store(&store, session, ids, lens, delimiter);
+            r = delim_index_store(&store, session, ids, lens, delimiter, quote);
           }
           return vector_to_array(std::move(r));
         },
-        py::arg("store"), py::arg("session"), py::arg("block_ids"), py::arg("block_lengths"), py::arg("delimiter"));
+        py::arg("store"), py::arg("session"), py::arg("block_ids"), py::arg("block_lengths"), py::arg("delimiter"),
+        py::arg("quote") = -1);
   // times=True: (cuts, (count_ms, scan_ms, emit_ms)) with the device time of the three launches.
   m.def("delim_index_raw",
         [](uint64_t arena, const std::vector<int64_t>& pages, uint64_t page_size, int device, uint64_t vstart,
-           uint64_t bytes, uint32_t delimiter, uint64_t add, bool times) -> py::object {
+           uint64_t bytes, uint32_t delimiter, uint64_t add, bool times, int64_t quote, bool in_quote) -> py::object {
           std::vector<uint64_t> r;
           DelimIndexTimes t;
           {
             py::gil_scoped_release rel;
-            r = delim_index_raw(arena, pages, page_size, device, vstart, bytes, delimiter, add, times ? &t : nullptr);
+            r = delim_index_raw(arena, pages, page_size, device, vstart, bytes, delimiter, add, times ? &t : nullptr,
+                                quote, in_quote);
           }
           py::object cuts = vector_to_array(std::move(r));
           if (!times) return cuts;
           return py::make_tuple(cuts, py::make_tuple(t.count_ms, t.scan_ms, t.emit_ms));
         },
         py::arg("arena_base"), py::arg("pages"), py::arg("page_size"), py::arg("device"), py::arg("vstart"),
-        py::arg("bytes"), py::arg("delimiter"), py::arg("add") = 0, py::arg("times") = false);
+        py::arg("bytes"), py::arg("delimiter"), py::arg("add") = 0, py::arg("times") = false,
+        py::arg("quote") = -1, py::arg("in_quote") = false);
   m.def("delim_index_launches", &delim_index_launches);
 
   // ---- native S3 data path (http_blob.cpp) --------------------------------------------------
@@ -1014,6 +1018,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("set_delim_index_variant", &set_delim_index_variant, py::arg("variant"), py::arg("tile_shift") = 0);
   m.def("delim_index_tile_shift", &delim_index_tile_shift);
   m.def("delim_index_variant", &delim_index_variant);
+  m.def("set_delim_quote_variant", &set_delim_quote_variant, py::arg("variant"));
+  m.def("delim_quote_variant", &delim_quote_variant);
   m.def("set_page_gather_chunk_variant", &set_page_gather_chunk_variant, py::arg("variant"));
   m.attr("COPY_CHUNK") = kCopyChunk;
 }

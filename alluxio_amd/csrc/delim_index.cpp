@@ -21,6 +21,13 @@ std::atomic<uint64_t> g_launches{0};
 
 void bad(const std::string& what) { throw StoreError(kErrInvalidArgument, "delimiter index: " + what); }
 
+void check_quote(uint32_t delim, int64_t quote, bool in_quote) {
+  if (delim > 255) bad("the delimiter is one byte");
+  if (quote < -1 || quote > 255) bad("the quote is one byte");
+  if (quote == (int64_t)delim) bad("the quote equals the delimiter");
+  if (in_quote && quote < 0) bad("in_quote without a quote");
+}
+
 // Device allocations and events of one call: released on every path out of it.
 struct DevMem {
   void* p = nullptr;
@@ -56,11 +63,17 @@ uint32_t shift_of(uint64_t page_size) {
 // The range has been validated against vtab.  on_device: the arena is device memory of the
 // current device.
 std::vector<uint64_t> run(uint64_t arena, const std::vector<int64_t>& vtab, uint32_t page_shift, bool on_device,
-                          uint64_t vstart, uint64_t bytes, uint32_t delim, uint64_t add, DelimIndexTimes* times) {
+                          uint64_t vstart, uint64_t bytes, uint32_t delim, uint64_t add, DelimIndexTimes* times,
+                          int64_t quote, bool in_quote) {
   std::vector<uint64_t> out;
   if (bytes == 0) return out;
+  const bool quoted = quote >= 0;
   if (!on_device) {
-    delim_index_host(reinterpret_cast<const uint8_t*>(arena), vtab.data(), page_shift, vstart, bytes, (uint8_t)delim,
+    if (quoted)
+      delim_index_host_quoted(reinterpret_cast<const uint8_t*>(arena), vtab.data(), page_shift, vstart, bytes,
+                              (uint8_t)delim, (uint8_t)quote, in_quote, add, &out);
+    else
+      delim_index_host(reinterpret_cast<const uint8_t*>(arena), vtab.data(), page_shift, vstart, bytes, (uint8_t)delim,
                      add, &out);
     return out;
   }
@@ -69,7 +82,7 @@ std::vector<uint64_t> run(uint64_t arena, const std::vector<int64_t>& vtab, uint
   a.tile_shift = delim_index_tile_shift();
   const uint64_t nt = delim_index_tiles(vstart, bytes, a.tile_shift);
   if (nt > (1ull << 30)) bad("range too large for one call");
-  DevMem d_vtab, d_count, d_base, d_out;
+  DevMem d_vtab, d_count, d_base, d_out, d_odd, d_parity;
   Events ev;
   // only the pages the range touches travel
   const uint64_t p0 = vstart >> page_shift, p1 = (vstart + bytes - 1) >> page_shift;
@@ -87,15 +100,23 @@ std::vector<uint64_t> run(uint64_t arena, const std::vector<int64_t>& vtab, uint
   a.ntiles = (uint32_t)nt;
   a.page_shift = page_shift;
   a.delim = delim;
+  if (quoted) {
+    d_odd.alloc(nt * sizeof(uint32_t));
+    d_parity.alloc((nt + 1) * sizeof(uint32_t));
+    a.tile_count_odd = static_cast<uint32_t*>(d_odd.p);
+    a.tile_parity = static_cast<uint32_t*>(d_parity.p);
+    a.quote = (uint32_t)quote;
+    a.in_quote = in_quote ? 1u : 0u;
+  }
   hipStream_t st = nullptr;
   if (times) {
     ev.create();
     DI_HIP(hipEventRecord(ev.e[0], st));
   }
-  DI_HIP(launch_delim_count(a, st));
+  DI_HIP(quoted ? launch_delim_count_quoted(a, st) : launch_delim_count(a, st));
   ++g_launches;
   if (times) DI_HIP(hipEventRecord(ev.e[1], st));
-  DI_HIP(launch_delim_scan(a, st));
+  DI_HIP(quoted ? launch_delim_scan_quoted(a, st) : launch_delim_scan(a, st));
   ++g_launches;
   if (times) DI_HIP(hipEventRecord(ev.e[2], st));
   uint64_t total = 0;
@@ -105,7 +126,7 @@ std::vector<uint64_t> run(uint64_t arena, const std::vector<int64_t>& vtab, uint
     d_out.alloc(total * sizeof(uint64_t));
     a.out = static_cast<uint64_t*>(d_out.p);
     a.out_cap = total;
-    DI_HIP(launch_delim_emit(a, total, st));
+    DI_HIP(quoted ? launch_delim_emit_quoted(a, total, st) : launch_delim_emit(a, total, st));
     ++g_launches;
   }
   if (times) {
@@ -144,21 +165,21 @@ uint64_t delim_index_launches() { return g_launches.load(); }
 
 std::vector<uint64_t> delim_index_raw(uint64_t arena_base, const std::vector<int64_t>& pages, uint64_t page_size,
                                       int device, uint64_t vstart, uint64_t bytes, uint32_t delim, uint64_t add,
-                                      DelimIndexTimes* times) {
+                                      DelimIndexTimes* times, int64_t quote, bool in_quote) {
   const uint32_t page_shift = shift_of(page_size);
-  if (delim > 255) bad("the delimiter is one byte");
+  check_quote(delim, quote, in_quote);
   const uint64_t vbytes = (uint64_t)pages.size() << page_shift;
   if (vstart > vbytes || bytes > vbytes - vstart) bad("range outside the page table");
   for (int64_t p : pages)
     if (p < 0) bad("negative arena page");
   if (device >= 0) DI_HIP(hipSetDevice(device));
-  return run(arena_base, pages, page_shift, device >= 0, vstart, bytes, delim, add, times);
+  return run(arena_base, pages, page_shift, device >= 0, vstart, bytes, delim, add, times, quote, in_quote);
 }
 
 std::vector<uint64_t> delim_index_store(BlockStore* store, int64_t session, const std::vector<int64_t>& ids,
-                                        const std::vector<uint64_t>& lens, uint32_t delim) {
+                                        const std::vector<uint64_t>& lens, uint32_t delim, int64_t quote) {
   if (ids.size() != lens.size()) bad("bad block list");
-  if (delim > 255) bad("the delimiter is one byte");
+  check_quote(delim, quote, false);
   Locks locks(store);
   std::vector<int64_t> vtab;
   int dir0 = -1;
@@ -194,7 +215,7 @@ std::vector<uint64_t> delim_index_store(BlockStore* store, int64_t session, cons
     if (!store->has_device()) throw StoreError(kErrInvalidState, "delimiter index: device dir without a device");
     store->use_device();
   }
-  return run(arena, vtab, page_shift, arena_device, 0, file_len, delim, 0, nullptr);
+  return run(arena, vtab, page_shift, arena_device, 0, file_len, delim, 0, nullptr, quote, false);
 }
 
 }  // namespace amdx

@@ -18,6 +18,14 @@
 //        lane travel through ONE 64-bit wave scan as four 16-bit fields (a field holds at most
 //        64 * 16 = 1024), so a delimiter's slot is tile_base[t] + the delimiters before it in
 //        address order.  No atomics: the output is the same on every run.
+//
+// Quoted form (the *_quoted kernels): a quote byte toggles "inside quotes" and only a delimiter
+// outside is a cut.  The state is a prefix parity, so it rides the same three launches: count
+// stores a tile's quote parity and its delimiters at even and odd parity relative to the tile's
+// start, scan turns the parities into each tile's incoming state and sums the matching counts,
+// emit starts from that state.  Inside a step the state before a lane's vector is the running
+// parity plus popcount(ballot(vector parity) & lanes below); inside a vector it is a prefix xor
+// of the quote flags (of the 16-bit mask in emit, of the 0x80 byte flags in count).
 #include "kernels.h"
 
 #include <algorithm>
@@ -224,8 +232,255 @@ __global__ __launch_bounds__(kDiThreads) void delim_emit_kernel(DelimIndexArgs a
   }
 }
 
-// Defaults from tools/delim_index_bench.py on MI355X (profiles/delim_index.md).
-int g_di_variant = 1;            // nontemporal loads: every byte is read once per launch
+// ---- quoted form --------------------------------------------------------------------------------
+// A byte that is neither the delimiter nor the quote: the content of a vector that was not loaded.
+__device__ __forceinline__ uint32_t di_neither(uint32_t d, uint32_t q) {
+  return (d != 0 && q != 0) ? 0u : ((d != 1 && q != 1) ? 1u : 2u);
+}
+
+// Bit j is set when an odd number of the bits below j is set in the 16-bit mask qm: byte j of the
+// vector lies inside quotes when the vector starts outside.
+__device__ __forceinline__ uint32_t di_inside16(uint32_t qm) {
+  uint32_t m = qm;
+  m ^= m << 1;
+  m ^= m << 2;
+  m ^= m << 4;
+  m ^= m << 8;
+  return (m << 1) & 0xFFFFu;
+}
+
+// The masks of one vector: dm = delimiters, qm = quotes, both limited to the bytes of the range.
+struct DiMasks {
+  uint32_t dm, qm;
+};
+__device__ __forceinline__ DiMasks di_masks(u32x4 v, uint32_t dw, uint32_t qw, uint64_t va, uint64_t vstart,
+                                            uint64_t t1) {
+  const uint32_t lo = va < vstart ? (uint32_t)(vstart - va) : 0u;
+  const uint32_t hi = va >= t1 ? 0u : (t1 - va < 16 ? (uint32_t)(t1 - va) : 16u);
+  DiMasks r;
+  r.dm = di_mask16(v, dw, lo, hi);
+  r.qm = di_mask16(v, qw, lo, hi);
+  return r;
+}
+
+// The delimiters of one vector that lie inside quotes.  par: the wave-uniform state before group
+// u of this step; it moves on to the state after the group.  Within a step the address order is
+// group u, then lane, so the state before this lane's vector is par plus the parity of the quote
+// bytes of the lanes below: one ballot, no shuffle scan.
+__device__ __forceinline__ uint32_t di_quoted_part(const DiMasks& k, uint32_t lane, uint32_t* par) {
+  const uint64_t b = __ballot(__popc(k.qm) & 1);
+  const uint32_t before = (*par ^ (uint32_t)__popcll(b & ((1ull << lane) - 1ull))) & 1u;
+  *par = (*par ^ (uint32_t)__popcll(b)) & 1u;
+  const uint32_t inq = di_inside16(k.qm) ^ (before ? 0xFFFFu : 0u);
+  return k.dm & inq;
+}
+
+// What the count kernel needs of one vector, relative to a vector that starts outside quotes:
+// all = its delimiters, odd = those of them inside quotes, par = the parity of its quote bytes.
+// The bytes stay where they are: di_match leaves 0x80 per matching byte, and as the lowest address
+// is the lowest byte of a word, p ^= p << 8; p ^= p << 16 turns the quote flags into the parity of
+// the quotes up to and including each byte, p << 8 into that of the quotes before it, and bit 31
+// of p carries on into the next word (m: all ones when the word starts inside).  No 16-bit mask
+// and none of its multiplies; only the two vectors that can hold bytes outside the range build one.
+struct DiRel {
+  uint32_t all, odd, par;
+};
+__device__ __forceinline__ DiRel di_rel(u32x4 v, uint32_t dw, uint32_t qw, uint64_t va, uint64_t vstart, uint64_t t1) {
+  DiRel r;
+  if (va < vstart || (va < t1 && t1 - va < 16)) {
+    const DiMasks k = di_masks(v, dw, qw, va, vstart, t1);
+    r.all = __popc(k.dm);
+    r.odd = __popc(k.dm & di_inside16(k.qm));
+    r.par = __popc(k.qm) & 1u;
+    return r;
+  }
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  uint32_t m = 0;
+  r.all = 0;
+  r.odd = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t dz = di_match(w[i], dw);
+    uint32_t p = di_match(w[i], qw);
+    p ^= p << 8;
+    p ^= p << 16;
+    r.all += __popc(dz);
+    r.odd += __popc(dz & ((p << 8) ^ m));
+    m ^= (uint32_t)((int32_t)p >> 31);
+  }
+  r.par = m & 1u;
+  return r;
+}
+
+// FAST: a step whose vectors hold no quote byte at all (one ballot; bytes outside the range make
+// it take the exact path, never a wrong one) adds the SWAR popcount to the counter of the running
+// parity.
+template <int NT, int FAST>
+__global__ __launch_bounds__(kDiThreads) void delim_count_quoted_kernel(DelimIndexArgs a) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kDiWaves + (threadIdx.x >> 6));
+  const uint32_t nwaves = gridDim.x * kDiWaves;
+  const uint32_t dw = (a.delim & 0xFFu) * 0x01010101u;
+  const uint32_t qw = (a.quote & 0xFFu) * 0x01010101u;
+  const uint32_t nw = di_neither(a.delim & 0xFFu, a.quote & 0xFFu) * 0x01010101u;
+  const u32x4 none = {nw, nw, nw, nw};
+  const uint64_t below = (1ull << lane) - 1ull;
+  for (uint32_t t = wave; t < a.ntiles; t += nwaves) {
+    const DiTile tl = di_tile(a, t);
+    uint32_t all = 0, odd = 0;
+    uint32_t par = 0;                               // relative to the tile's start (wave-uniform)
+    for (uint64_t vb = tl.t0; vb < tl.t1; vb += 64 * 16 * kDiUnroll) {
+      u32x4 d[kDiUnroll];
+#pragma unroll
+      for (int u = 0; u < kDiUnroll; ++u) {
+        const uint64_t va = vb + ((uint64_t)u * 64 + lane) * 16;
+        d[u] = none;
+        if (va < tl.t1) d[u] = di_load<NT>(a, va);
+      }
+      if constexpr (FAST) {
+        uint32_t any = 0;
+#pragma unroll
+        for (int u = 0; u < kDiUnroll; ++u)
+          any |= di_match(d[u].x, qw) | di_match(d[u].y, qw) | di_match(d[u].z, qw) | di_match(d[u].w, qw);
+        if (__ballot(any != 0) == 0ull) {           // wave-uniform
+          uint32_t c = 0;
+#pragma unroll
+          for (int u = 0; u < kDiUnroll; ++u)
+            c += di_count(d[u], dw, vb + ((uint64_t)u * 64 + lane) * 16, a.vstart, tl.t1);
+          all += c;
+          if (par) odd += c;
+          continue;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kDiUnroll; ++u) {
+        const DiRel r = di_rel(d[u], dw, qw, vb + ((uint64_t)u * 64 + lane) * 16, a.vstart, tl.t1);
+        // address order is group u, then lane: the state before this vector is the running parity
+        // plus the parity of the quote bytes of the lanes below (one ballot, no shuffle scan)
+        const uint64_t b = __ballot(r.par);
+        const uint32_t before = (par ^ (uint32_t)__popcll(b & below)) & 1u;
+        par = (par ^ (uint32_t)__popcll(b)) & 1u;
+        all += r.all;
+        odd += before ? r.all - r.odd : r.odd;
+      }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+      all += __shfl_xor(all, s);
+      odd += __shfl_xor(odd, s);
+    }
+    if (lane == 0) {
+      a.tile_count[t] = all - odd;
+      a.tile_count_odd[t] = odd;
+      a.tile_parity[t] = par;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kScanThreads) void delim_scan_quoted_kernel(DelimIndexArgs a) {
+  __shared__ uint64_t sh[kScanThreads / 64 + 1];
+  uint64_t carry = 0;
+  uint32_t state = a.in_quote & 1u;                 // before the round's first tile
+  for (uint32_t base = 0; base < a.ntiles; base += kScanThreads * kScanItems) {
+    const uint32_t r0 = base + threadIdx.x * kScanItems;
+    uint32_t ce[kScanItems], co[kScanItems], pq[kScanItems];
+    uint64_t psum = 0;
+#pragma unroll
+    for (int i = 0; i < kScanItems; ++i) {
+      const bool in = r0 + i < a.ntiles;
+      ce[i] = in ? a.tile_count[r0 + i] : 0u;
+      co[i] = in ? a.tile_count_odd[r0 + i] : 0u;
+      pq[i] = in ? a.tile_parity[r0 + i] & 1u : 0u;
+      psum += pq[i];
+    }
+    uint64_t ptotal;
+    uint32_t s = (state + (uint32_t)di_scan(psum, sh, &ptotal)) & 1u;   // before this thread's first tile
+    state = (state + (uint32_t)ptotal) & 1u;
+    uint32_t c[kScanItems];
+    uint64_t sum = 0;
+#pragma unroll
+    for (int i = 0; i < kScanItems; ++i) {
+      c[i] = s ? co[i] : ce[i];
+      sum += c[i];
+      if (r0 + i < a.ntiles) a.tile_parity[r0 + i] = s;
+      s ^= pq[i];
+    }
+    uint64_t total;
+    uint64_t off = carry + di_scan(sum, sh, &total);
+    carry += total;
+#pragma unroll
+    for (int i = 0; i < kScanItems; ++i) {
+      if (r0 + i < a.ntiles) a.tile_base[r0 + i] = off;
+      off += c[i];
+    }
+  }
+  if (threadIdx.x == 0) {
+    a.tile_base[a.ntiles] = carry;
+    a.tile_parity[a.ntiles] = state;
+  }
+}
+
+template <int NT>
+__global__ __launch_bounds__(kDiThreads) void delim_emit_quoted_kernel(DelimIndexArgs a) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kDiWaves + (threadIdx.x >> 6));
+  const uint32_t nwaves = gridDim.x * kDiWaves;
+  const uint32_t dw = (a.delim & 0xFFu) * 0x01010101u;
+  const uint32_t qw = (a.quote & 0xFFu) * 0x01010101u;
+  const uint32_t nw = di_neither(a.delim & 0xFFu, a.quote & 0xFFu) * 0x01010101u;
+  const u32x4 none = {nw, nw, nw, nw};
+  for (uint32_t t = wave; t < a.ntiles; t += nwaves) {
+    const DiTile tl = di_tile(a, t);
+    uint64_t run = a.tile_base[t];                  // slot of the tile's next cut (wave-uniform)
+    uint32_t par = __builtin_amdgcn_readfirstlane(a.tile_parity[t]) & 1u;   // the tile's incoming state
+    for (uint64_t vb = tl.t0; vb < tl.t1; vb += 64 * 16 * kDiUnroll) {
+      u32x4 d[kDiUnroll];
+#pragma unroll
+      for (int u = 0; u < kDiUnroll; ++u) {
+        const uint64_t va = vb + ((uint64_t)u * 64 + lane) * 16;
+        d[u] = none;
+        if (va < tl.t1) d[u] = di_load<NT>(a, va);
+      }
+      uint32_t m[kDiUnroll];
+      uint64_t p = 0;
+#pragma unroll
+      for (int u = 0; u < kDiUnroll; ++u) {
+        const DiMasks k = di_masks(d[u], dw, qw, vb + ((uint64_t)u * 64 + lane) * 16, a.vstart, tl.t1);
+        m[u] = k.dm ^ di_quoted_part(k, lane, &par);      // dm & ~inside
+        p |= (uint64_t)__popc(m[u]) << (16 * u);
+      }
+      if (__ballot(p != 0) == 0ull) continue;       // wave-uniform; par has moved past the step
+      uint64_t inc = p;
+#pragma unroll
+      for (int s = 1; s < 64; s <<= 1) {
+        const uint64_t o = __shfl_up((unsigned long long)inc, s);
+        if ((int)lane >= s) inc += o;
+      }
+      const uint64_t tot = __shfl((unsigned long long)inc, 63);
+      const uint64_t exc = inc - p;
+#pragma unroll
+      for (int u = 0; u < kDiUnroll; ++u) {
+        const uint64_t va = vb + ((uint64_t)u * 64 + lane) * 16;
+        uint64_t pos = run + ((exc >> (16 * u)) & 0xFFFFu);
+        uint32_t mm = m[u];
+        while (mm) {
+          const uint32_t j = (uint32_t)__builtin_ctz(mm);
+          if (pos < a.out_cap) a.out[pos] = a.add + (va + j - a.vstart) + 1;
+          ++pos;
+          mm &= mm - 1;
+        }
+        run += (tot >> (16 * u)) & 0xFFFFu;
+      }
+    }
+  }
+}
+
+// Defaults from tools/delim_index_bench.py on MI355X (profiles/delim_index.md, delim_index_quoted.md).
+// Count variant 1 is 6..19 % faster in count on a file without any quote and up to 8 % slower at
+// a CSV-like quote density; the three launches together differ by 1..6 % either way, about their
+// spread, so the simpler one is the default.
+int g_di_quote_variant = 0;
+int g_di_variant = 1;           // nontemporal loads: every byte is read once per launch
 uint32_t g_di_tile_shift = 15;   // 32 KiB per wave
 unsigned g_di_grid_cap = 2048;   // 256 CUs x 8 workgroups of 4 waves
 
@@ -236,6 +491,11 @@ hipError_t di_check(const DelimIndexArgs& a) {
   const uint64_t nt = delim_index_tiles(a.vstart, a.bytes, a.tile_shift);
   if (nt == 0 || nt > kDiMaxTiles || nt != a.ntiles) return hipErrorInvalidValue;
   return hipSuccess;
+}
+
+hipError_t di_check_quoted(const DelimIndexArgs& a) {
+  if (a.quote > 255 || a.quote == a.delim || a.in_quote > 1) return hipErrorInvalidValue;
+  return di_check(a);
 }
 
 unsigned di_grid(const DelimIndexArgs& a) {
@@ -281,6 +541,42 @@ hipError_t launch_delim_emit(const DelimIndexArgs& a, uint64_t total, hipStream_
   if (total == 0) return hipSuccess;
   if (g_di_variant == 1) hipLaunchKernelGGL(delim_emit_kernel<1>, dim3(di_grid(a)), dim3(kDiThreads), 0, stream, a);
   else hipLaunchKernelGGL(delim_emit_kernel<0>, dim3(di_grid(a)), dim3(kDiThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
+void set_delim_quote_variant(int variant) { g_di_quote_variant = variant ? 1 : 0; }
+
+int delim_quote_variant() { return g_di_quote_variant; }
+
+hipError_t launch_delim_count_quoted(const DelimIndexArgs& a, hipStream_t stream) {
+  const hipError_t c = di_check_quoted(a);
+  if (c != hipSuccess) return c;
+  const dim3 grid(di_grid(a)), block(kDiThreads);
+  if (g_di_variant == 1) {
+    if (g_di_quote_variant == 1) hipLaunchKernelGGL((delim_count_quoted_kernel<1, 1>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((delim_count_quoted_kernel<1, 0>), grid, block, 0, stream, a);
+  } else {
+    if (g_di_quote_variant == 1) hipLaunchKernelGGL((delim_count_quoted_kernel<0, 1>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((delim_count_quoted_kernel<0, 0>), grid, block, 0, stream, a);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_delim_scan_quoted(const DelimIndexArgs& a, hipStream_t stream) {
+  const hipError_t c = di_check_quoted(a);
+  if (c != hipSuccess) return c;
+  hipLaunchKernelGGL(delim_scan_quoted_kernel, dim3(1), dim3(kScanThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_delim_emit_quoted(const DelimIndexArgs& a, uint64_t total, hipStream_t stream) {
+  const hipError_t c = di_check_quoted(a);
+  if (c != hipSuccess) return c;
+  if (total > a.out_cap) return hipErrorInvalidValue;
+  if (total == 0) return hipSuccess;
+  if (g_di_variant == 1)
+    hipLaunchKernelGGL(delim_emit_quoted_kernel<1>, dim3(di_grid(a)), dim3(kDiThreads), 0, stream, a);
+  else hipLaunchKernelGGL(delim_emit_quoted_kernel<0>, dim3(di_grid(a)), dim3(kDiThreads), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // Host form of the delimiter index (see DelimIndexArgs in kernels.h): a memchr loop per page of a
-// virtual byte range behind a page table.  No HIP include, so a stand-alone program can compile it.
+// virtual byte range behind a page table, and its quoted form, which carries the state "inside
+// quotes" along.  No HIP include, so a stand-alone program can compile it.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -26,6 +27,38 @@ inline void delim_index_host(const uint8_t* arena, const int64_t* vtab, uint32_t
     }
     done += take;
   }
+}
+
+// The quoted form: a byte equal to `quote` (!= delim) toggles the state "inside quotes", which is
+// `in_quote` at vstart, and only a delimiter outside quotes is a cut.  Same contract otherwise.
+// Returns the state after the last byte.
+inline bool delim_index_host_quoted(const uint8_t* arena, const int64_t* vtab, uint32_t page_shift, uint64_t vstart,
+                                    uint64_t bytes, uint8_t delim, uint8_t quote, bool in_quote, uint64_t add,
+                                    std::vector<uint64_t>* out) {
+  const uint64_t psize = 1ull << page_shift, pmask = psize - 1;
+  uint64_t done = 0;
+  bool inside = in_quote;
+  while (done < bytes) {
+    const uint64_t va = vstart + done, po = va & pmask;
+    const uint64_t take = std::min(bytes - done, psize - po);
+    const uint8_t* p = arena + ((uint64_t)vtab[va >> page_shift] << page_shift) + po;
+    const uint8_t* e = p + take;
+    const uint8_t* q = p;
+    while (q < e) {
+      if (inside) {                                 // nothing counts up to the closing quote
+        q = static_cast<const uint8_t*>(std::memchr(q, quote, (size_t)(e - q)));
+        if (!q) break;
+        inside = false;
+        ++q;
+        continue;
+      }
+      const uint8_t b = *q++;
+      if (b == quote) inside = true;
+      else if (b == delim) out->push_back(add + done + (uint64_t)(q - p));
+    }
+    done += take;
+  }
+  return inside;
 }
 
 }  // namespace amdx

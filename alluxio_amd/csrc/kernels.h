@@ -136,11 +136,37 @@ struct DelimIndexArgs {
   uint32_t page_shift;
   uint32_t tile_shift;      // from delim_index_tile_shift()
   uint32_t delim;           // one byte
+  // Quoted form only (launch_delim_*_quoted; the unquoted launches ignore these):
+  uint32_t quote;           // one byte, != delim
+  uint32_t in_quote;        // 0 or 1: the state at vstart
+  uint32_t* tile_count_odd; // [ntiles] workspace
+  uint32_t* tile_parity;    // [ntiles + 1] workspace
 };
 uint64_t delim_index_tiles(uint64_t vstart, uint64_t bytes, uint32_t tile_shift);
 hipError_t launch_delim_count(const DelimIndexArgs& a, hipStream_t stream);
 hipError_t launch_delim_scan(const DelimIndexArgs& a, hipStream_t stream);
 hipError_t launch_delim_emit(const DelimIndexArgs& a, uint64_t total, hipStream_t stream);
+// Quoted form: every byte equal to `quote` toggles the state "inside quotes" (in_quote at vstart)
+// and a delimiter is a cut only outside, i.e. when the number of quote bytes before it in the
+// range plus in_quote is even.  The same three launches, still without atomics or any wait of
+// one workgroup on another; the tiles talk through the scan alone:
+//   count: a tile does not know its incoming state, so it stores the parity of its quote bytes
+//          (tile_parity[t]) and its delimiters at even (tile_count[t]) and at odd
+//          (tile_count_odd[t]) quote parity relative to the tile's start.
+//   scan:  carries the running parity and the running count across its rounds; per tile it turns
+//          tile_parity[t] into the tile's incoming state, picks the even or the odd count by it
+//          and prefix-sums the pick into tile_base.  tile_base[ntiles] = total as above,
+//          tile_parity[ntiles] = the state after the last byte.
+//   emit:  re-reads the tile from tile_parity[t] on and keeps the delimiters outside quotes.
+// The launchers re-check quote <= 255, quote != delim and in_quote <= 1.
+hipError_t launch_delim_count_quoted(const DelimIndexArgs& a, hipStream_t stream);
+hipError_t launch_delim_scan_quoted(const DelimIndexArgs& a, hipStream_t stream);
+hipError_t launch_delim_emit_quoted(const DelimIndexArgs& a, uint64_t total, hipStream_t stream);
+// Count kernel of the quoted form: 0 (default) = every step works out the state of each byte,
+// 1 = a step without a quote byte (one ballot) takes the SWAR popcount of the unquoted kernel
+// into the counter chosen by the running parity.
+void set_delim_quote_variant(int variant);
+int delim_quote_variant();
 // variant: 0 = plain loads, 1 (default) = nontemporal loads.  tile_shift (0 = keep; 10..24) sets the bytes
 // one wave owns.
 void set_delim_index_variant(int variant, unsigned tile_shift);

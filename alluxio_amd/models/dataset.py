@@ -213,7 +213,19 @@ def _delimiter_byte(delimiter) -> int:
     return d[0]
 
 
-def _store_cuts(fs, lay: _FileLayout, delim: int):
+def _quote_byte(quote, delim: int):
+    """None, or the one byte of ``quote``; it may not equal the delimiter."""
+    if quote is None:
+        return None
+    q = quote.encode() if isinstance(quote, str) else bytes(quote)
+    if len(q) != 1:
+        raise ValueError(f"the quote must be exactly one byte, got {len(q)}")
+    if q[0] == delim:
+        raise ValueError("the quote must differ from the delimiter")
+    return q[0]
+
+
+def _store_cuts(fs, lay: _FileLayout, delim: int, quote=None):
     """Cut positions of one file from the worker's own memory (``delim_index_store``: kernels for
     an HBM dir, the host loop for a DRAM dir), or None when the loader's rule sends the file to
     the stream path: a block not held by one in-process worker, or a layout the native call
@@ -232,7 +244,9 @@ def _store_cuts(fs, lay: _FileLayout, delim: int):
     ids_ = [int(b) for b in lay.block_ids]
     lens = [min(lay.block_size, lay.length - k * lay.block_size) for k in range(len(ids_))]
     try:
-        return lib().delim_index_store(w.native, ids.create_session_id(), ids_, lens, delim)
+        if quote is None:
+            return lib().delim_index_store(w.native, ids.create_session_id(), ids_, lens, delim)
+        return lib().delim_index_store(w.native, ids.create_session_id(), ids_, lens, delim, quote=quote)
     except lib().StoreError as e:
         if len(e.args) >= 1 and e.args[0] in (1, 6):     # block gone or a layout the call does not take
             return None
@@ -240,26 +254,42 @@ def _store_cuts(fs, lay: _FileLayout, delim: int):
         raise translate(e) from None
 
 
-def _stream_cuts(fs, path: str, delim: int, chunk_bytes: int) -> np.ndarray:
-    """The same cut positions from the client stream, ``chunk_bytes`` at a time."""
-    parts, pos = [], 0
+def _stream_cuts(fs, path: str, delim: int, chunk_bytes: int, quote=None) -> np.ndarray:
+    """The same cut positions from the client stream, ``chunk_bytes`` at a time.  With a quote the
+    state "inside quotes" (the parity of the quote bytes so far) travels from chunk to chunk."""
+    parts, pos, state = [], 0, 0
     buf = np.empty(max(1, int(chunk_bytes)), dtype=np.uint8)
     with fs.open_file(path) as f:
         while True:
             n = f.readinto(buf)
             if n <= 0:
                 break
-            parts.append(np.flatnonzero(buf[:n] == delim).astype(np.uint64) + np.uint64(pos + 1))
+            hit = buf[:n] == delim
+            if quote is not None:
+                # the state after each byte, relative to the chunk's start; a delimiter is no quote,
+                # so at a delimiter it is also the state before it
+                inside = np.logical_xor.accumulate(buf[:n] == quote)
+                hit &= inside if state else ~inside     # an even number of quote bytes before it
+                state ^= int(inside[-1])
+            parts.append(np.flatnonzero(hit).astype(np.uint64) + np.uint64(pos + 1))
             pos += n
     return np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint64)
 
 
-def build_delimited_index(fs, path: str, delimiter=b"\n", write: bool = False, device_plan="auto",
+def build_delimited_index(fs, path: str, delimiter=b"\n", quote=None, write: bool = False, device_plan="auto",
                           chunk_bytes: int = 8 << 20, **write_kw) -> np.ndarray:
     """The record index of a delimited text file (JSONL, CSV, one document per line): int64 offsets
     ``[0, every cut ..., file length]`` where a cut is the byte after a delimiter, so records keep
     their trailing delimiter (``bytes.splitlines(keepends=True)`` for ``\\n``), a last line without
     one is a record and an empty file gives ``[0]``.
+
+    ``quote`` (one byte, not the delimiter; ``'"'`` for CSV) makes the index quote-aware: every
+    quote byte toggles the state "inside quotes", the file starts outside, and a delimiter is a cut
+    only when the number of quote bytes before it is even.  A doubled quote ``""`` toggles twice,
+    so this is the record structure of every well-formed RFC 4180 file, line breaks inside quoted
+    fields included.  It is not the ``csv`` module's lenient reading of a stray quote in the
+    middle of an unquoted field: there the two disagree.  A file that ends inside quotes is no
+    error; its tail is the last record.
 
     When one in-process worker holds every block in one memory dir the delimiters are found where
     the bytes are (count, scan and emit kernels through the page table for an HBM dir, a memchr
@@ -267,14 +297,15 @@ def build_delimited_index(fs, path: str, delimiter=b"\n", write: bool = False, d
     client stream ``chunk_bytes`` at a time.  All paths return the same array.  ``write=True`` also
     stores it as the ``<path>.idx`` sidecar (``write_kw`` goes to :func:`write_index`)."""
     delim = _delimiter_byte(delimiter)
+    quote = _quote_byte(quote, delim)
     if device_plan not in ("auto", False):
         raise ValueError("device_plan must be 'auto' or False")
     lay = _FileLayout(fs.get_status(path))
     cuts = None
     if device_plan == "auto" and lay.length and len(lay.block_ids):
-        cuts = _store_cuts(fs, lay, delim)
+        cuts = _store_cuts(fs, lay, delim, quote)
     if cuts is None:
-        cuts = _stream_cuts(fs, path, delim, chunk_bytes) if lay.length else np.zeros(0, dtype=np.uint64)
+        cuts = _stream_cuts(fs, path, delim, chunk_bytes, quote) if lay.length else np.zeros(0, dtype=np.uint64)
     off = np.empty(cuts.size + 2, dtype=np.int64)
     off[0] = 0
     off[1:-1] = cuts
@@ -373,12 +404,14 @@ class IndexedRecordDataset:
         return self
 
     @classmethod
-    def from_delimited(cls, fs, paths, delimiter=b"\n", dtype="uint8", device=None, write_index: bool = False):
+    def from_delimited(cls, fs, paths, delimiter=b"\n", dtype="uint8", device=None, write_index: bool = False,
+                       quote=None):
         """One record per line (or per ``delimiter``-terminated piece) of one or more text files:
         the index of each file comes from :func:`build_delimited_index`, and ``write_index=True``
-        also stores it as the file's ``.idx`` sidecar."""
+        also stores it as the file's ``.idx`` sidecar.  ``quote='"'`` keeps a CSV row with line
+        breaks inside quoted fields in one record (see :func:`build_delimited_index`)."""
         paths = [paths] if isinstance(paths, str) else list(paths)
-        index = [build_delimited_index(fs, p, delimiter, write=write_index) for p in paths]
+        index = [build_delimited_index(fs, p, delimiter, quote=quote, write=write_index) for p in paths]
         return cls(fs, paths, index=index, dtype=dtype, device=device)
 
     def __len__(self):

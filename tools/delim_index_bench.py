@@ -16,6 +16,14 @@ Per file size (``--sizes``, MiB; 128 is cache-resident, 16384 HBM-resident) and 
 The result of every (a) configuration is compared with numpy (``--check-mib`` and below) or, for
 larger files, with a device-side count of the delimiter plus a strict-ascent check.  One JSON line
 per measurement goes to stdout and to ``--out``.  Needs a GPU: it fails without one.
+
+``--quoted`` measures the quote-aware index (``quote='"'``) instead: per size and line length and
+per quote density of ``--quote-densities`` (quote bytes per byte; 0 = no quote in the file), the
+text gets quote bytes at that density and ``--inside-share`` of its newlines moved inside quoted
+fields.  Rounds alternate unquoted / quoted count variant 0 / quoted count variant 1 over the same
+bytes, so the record holds the per-launch device times of all three and the ratios.  Every
+configuration is compared with the quote-parity rule first: in numpy up to ``--check-mib``, by a
+device-side prefix sum above.  The end-to-end phase then runs ``build_delimited_index(quote='"')``.
 """
 import argparse
 import json
@@ -57,6 +65,129 @@ def fill_text(torch, arena, line_len, seed):
         part[torch.rand(part.numel(), device="cuda", generator=g) < 1.0 / line_len] = DELIM
         count += int((part == DELIM).sum().item())
     return count
+
+
+QUOTE = 0x22
+
+
+def fill_csv(torch, arena, line_len, density, inside_share, seed):
+    """fill_text plus quote bytes: about `density` of the bytes are quotes, placed so that about
+    `inside_share` of the newlines fall inside quotes (a newline's own state is drawn first, then
+    quotes are planted where the state has to change)."""
+    g = torch.Generator(device="cuda")
+    g.manual_seed(seed)
+    for s in range(0, arena.numel(), GEN):
+        part = arena[s:s + GEN]
+        part.view(torch.int64).random_(generator=g)
+        part[(part == DELIM) | (part == QUOTE)] = 0x20
+        part[torch.rand(part.numel(), device="cuda", generator=g) < 1.0 / line_len] = DELIM
+        if density > 0:
+            # pairs of quotes (an opening and a closing one) at density / 2, a field length chosen so
+            # that the share of bytes inside quotes is about inside_share
+            n = part.numel()
+            opens = torch.nonzero(torch.rand(n, device="cuda", generator=g) < density / 2).flatten()
+            gap = max(1, int(2 * inside_share / density))
+            closes = opens + 1 + (torch.rand(opens.numel(), device="cuda", generator=g) * 2 * gap).long()
+            closes = closes[closes < n]
+            part[opens] = QUOTE
+            part[closes] = QUOTE
+
+
+def rule_device(torch, arena, pages_t, nbytes):
+    """(number of cuts, their sum) by the quote-parity rule, from device-side prefix sums over the
+    virtual byte order, page by page with the state carried."""
+    state, count, total, pos = 0, 0, 0, 0
+    step = 4096                                         # pages per batch
+    for i in range(0, pages_t.numel(), step):
+        idx = pages_t[i:i + step]
+        virt = arena.view(-1, PAGE)[idx].reshape(-1)
+        virt = virt[:max(0, min(virt.numel(), nbytes - pos))]
+        if virt.numel() == 0:
+            break
+        q = (virt == QUOTE)
+        seen = torch.cumsum(q, 0, dtype=torch.int64)
+        hit = (virt == DELIM) & (((seen - q.long() + state) & 1) == 0)
+        where = torch.nonzero(hit).flatten()
+        count += int(where.numel())
+        total += int((where + (pos + 1)).sum().item())
+        state = (state + int(seen[-1].item())) & 1
+        pos += virt.numel()
+    return count, total
+
+
+def quoted_phase(torch, C, size, line_len, density, a):
+    npages = size // PAGE
+    arena = torch.empty(npages * PAGE, dtype=torch.uint8, device="cuda")
+    fill_csv(torch, arena, line_len, density, a.inside_share, seed=line_len)
+    pages = np.random.default_rng(1).permutation(npages).astype(np.int64)
+    plist = pages.tolist()
+    nbytes = size - 12345                               # the file ends inside its last page
+    want = want_sum = None
+    if size <= a.check_mib << 20:
+        virt = arena.cpu().numpy().reshape(npages, PAGE)[pages].reshape(-1)[:nbytes]
+        q = virt == QUOTE
+        before = np.cumsum(q) - q
+        want = (np.flatnonzero((virt == DELIM) & (before % 2 == 0)) + 1).astype(np.uint64)
+        want_n, newlines = want.size, int((virt == DELIM).sum())
+        del virt, q, before
+    else:
+        want_n, want_sum = rule_device(torch, arena, torch.from_numpy(pages).cuda(), nbytes)
+        newlines = None
+    default_q = C.delim_quote_variant()
+
+    def call(mode):
+        if mode == "plain":
+            return C.delim_index_raw(arena.data_ptr(), plist, PAGE, 0, 0, nbytes, DELIM, 0, True)
+        C.set_delim_quote_variant(mode)
+        return C.delim_index_raw(arena.data_ptr(), plist, PAGE, 0, 0, nbytes, DELIM, 0, True, quote=QUOTE)
+
+    for mode in (0, 1):                                 # check each configuration before timing it
+        cuts, _ = call(mode)
+        ok = np.array_equal(cuts, want) if want is not None else (
+            cuts.size == want_n and int(cuts.astype(np.int64).sum()) == want_sum
+            and bool((np.diff(cuts.view(np.int64)) > 0).all()))
+        if not ok:
+            raise SystemExit(f"wrong quoted index: count variant {mode} size {size} density {density}")
+        del cuts
+    call("plain")
+    rounds = a.rounds if size <= 1 << 30 else max(3, a.rounds // 3)
+    res = {"plain": [], 0: [], 1: []}
+    for _ in range(rounds):
+        for mode in res:                                # A/B/C/A/B/C
+            _, ms = call(mode)
+            res[mode].append(ms)
+    C.set_delim_quote_variant(default_q)
+    med = {}
+    for mode, xs in res.items():
+        tot = spread([sum(x) for x in xs], 3)
+        med[mode] = tot["median"]
+        emit({"what": "quoted_kernels", "size_mib": size >> 20, "line_len": line_len, "quote_density": density,
+              "inside_share": a.inside_share if density else 0, "mode": "unquoted" if mode == "plain" else f"quoted_c{mode}",
+              "cuts": want_n if mode != "plain" else None, "newlines": newlines,
+              "tile_bytes": 1 << C.delim_index_tile_shift(), "GBps": spread([nbytes / (sum(x) * 1e-3) / 1e9 for x in xs]),
+              "count_ms": spread([x[0] for x in xs], 3), "scan_ms": spread([x[1] for x in xs], 3),
+              "emit_ms": spread([x[2] for x in xs], 3), "total_ms": tot}, a.out)
+    emit({"what": "quoted_ratio", "size_mib": size >> 20, "line_len": line_len, "quote_density": density,
+          "quoted_c0_over_unquoted": round(med[0] / med["plain"], 3),
+          "quoted_c1_over_unquoted": round(med[1] / med["plain"], 3),
+          "count_c1_over_c0": round(spread([x[0] for x in res[1]], 3)["median"] /
+                                    spread([x[0] for x in res[0]], 3)["median"], 3)}, a.out)
+    del arena
+    torch.cuda.empty_cache()
+
+
+def csv_chunk(line_len, density, inside_share, n=64 << 20):
+    rng = np.random.default_rng(7)
+    chunk = rng.integers(0, 256, n, dtype=np.uint8)
+    chunk[(chunk == DELIM) | (chunk == QUOTE)] = 0x20
+    chunk[rng.random(n) < 1.0 / line_len] = DELIM
+    if density > 0:
+        opens = np.flatnonzero(rng.random(n) < density / 2)
+        gap = max(1, int(2 * inside_share / density))
+        closes = opens + 1 + (rng.random(opens.size) * 2 * gap).astype(np.int64)
+        chunk[opens] = QUOTE
+        chunk[closes[closes < n]] = QUOTE
+    return chunk
 
 
 def kernel_phase(torch, C, size, line_len, a):
@@ -138,17 +269,20 @@ def kernel_phase(torch, C, size, line_len, a):
     torch.cuda.empty_cache()
 
 
-def e2e_phase(torch, size, line_len, a):
+def e2e_phase(torch, size, line_len, a, quote=None, density=0.0):
     from alluxio_amd.minicluster import LocalAlluxioCluster
     from alluxio_amd.models import build_delimited_index
     conf = {"alluxio.worker.tieredstore.level0.dirs.path": "hbm:0",
             "alluxio.worker.tieredstore.level0.dirs.quota": str(size + (512 << 20)),
             "alluxio.worker.hbm.page.size": "64KB",
             "alluxio.user.block.size.bytes.default": "64MB"}
-    rng = np.random.default_rng(7)
-    chunk = rng.integers(0, 256, 64 << 20, dtype=np.uint8)
-    chunk[chunk == DELIM] = 0x20
-    chunk[rng.random(chunk.size) < 1.0 / line_len] = DELIM
+    if quote is None:
+        rng = np.random.default_rng(7)
+        chunk = rng.integers(0, 256, 64 << 20, dtype=np.uint8)
+        chunk[chunk == DELIM] = 0x20
+        chunk[rng.random(chunk.size) < 1.0 / line_len] = DELIM
+    else:
+        chunk = csv_chunk(line_len, density, a.inside_share)
     with LocalAlluxioCluster(num_workers=1, conf=conf) as c:
         fs = c.client()
         with fs.create_file("/text/e2e.jsonl", write_type="MUST_CACHE") as f:
@@ -162,13 +296,14 @@ def e2e_phase(torch, size, line_len, a):
         for it in range(a.e2e_rounds + 1):
             for plan in ("auto", False):                # A/B/A/B
                 t = time.perf_counter()
-                off = build_delimited_index(fs, "/text/e2e.jsonl", device_plan=plan)
+                off = build_delimited_index(fs, "/text/e2e.jsonl", quote=quote, device_plan=plan)
                 dt = time.perf_counter() - t
                 first.setdefault(plan, off)
                 if it:
                     res[plan].append(dt * 1e3)
         same = bool(np.array_equal(first["auto"], first[False]))
-        emit({"what": "end_to_end", "size_mib": size >> 20, "line_len": line_len, "records": int(first["auto"].size - 1),
+        emit({"what": "end_to_end", "quote": quote, "quote_density": density,
+              "size_mib": size >> 20, "line_len": line_len, "records": int(first["auto"].size - 1),
               "device_ms": spread(res["auto"], 1), "stream_numpy_ms": spread(res[False], 1), "equal": same,
               "speedup": round(spread(res[False])["median"] / spread(res["auto"])["median"], 1)}, a.out)
         if not same:
@@ -186,6 +321,9 @@ def main():
     ap.add_argument("--e2e-mib", type=int, default=1024, help="file of the end-to-end phase (0: skip)")
     ap.add_argument("--e2e-rounds", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--quoted", action="store_true", help="measure the quote-aware index instead")
+    ap.add_argument("--quote-densities", default="0,0.02", help="quote bytes per byte (0: no quote in the file)")
+    ap.add_argument("--inside-share", type=float, default=0.3, help="share of the bytes (and newlines) inside quotes")
     a = ap.parse_args()
     a.shifts = [int(s) for s in a.shifts.split(",")]
     import torch
@@ -197,6 +335,16 @@ def main():
         os.remove(a.out)
     emit({"what": "setup", "device": torch.cuda.get_device_name(0), "page": PAGE, "rounds": a.rounds,
           "default_tile_bytes": 1 << C.delim_index_tile_shift()}, a.out)
+    if a.quoted:
+        densities = [float(x) for x in a.quote_densities.split(",")]
+        for size in (int(s) << 20 for s in a.sizes.split(",")):
+            for line_len in (int(x) for x in a.lines.split(",")):
+                for density in densities:
+                    quoted_phase(torch, C, size, line_len, density, a)
+        if a.e2e_mib:
+            for line_len in (int(x) for x in a.lines.split(",")):
+                e2e_phase(torch, a.e2e_mib << 20, line_len, a, quote='"', density=max(densities))
+        return
     for size in (int(s) << 20 for s in a.sizes.split(",")):
         for line_len in (int(x) for x in a.lines.split(",")):
             kernel_phase(torch, C, size, line_len, a)
