@@ -16,6 +16,7 @@
 #include "ring_read.h"
 #include "ragged_gather.h"
 #include "delim_index.h"
+#include "field_parse.h"
 #include "kernels.h"
 #include "seg_ring.h"
 #include "frame_rpc.h"
@@ -677,6 +678,34 @@ PYBIND11_MODULE(_C, m) {
         py::arg("quote") = -1, py::arg("in_quote") = false);
   m.def("delim_index_launches", &delim_index_launches);
 
+  // ---- typed columns from delimited text rows (field_parse.cpp) ------------------------------
+  // cols: (field number, type 0 span / 1 int64 / 2 int32 / 3 float64 / 4 float32, values pointer,
+  // span-length pointer or 0, status pointer).  device < 0: host memory, done on return; otherwise
+  // the kernel is queued on `stream`.
+  m.def("field_parse_raw",
+        [](uint64_t data, uint64_t data_bytes, uint64_t off, uint64_t len, bool len_is_64, uint64_t nrows, int device,
+           const std::vector<std::tuple<uint64_t, uint32_t, uint64_t, uint64_t, uint64_t>>& cols, uint32_t sep,
+           int64_t quote, uint32_t terminator, uint64_t stream) {
+          std::vector<FieldParseCol> cs;
+          cs.reserve(cols.size());
+          for (auto& c : cols) {
+            FieldParseCol x{};
+            // out-of-range numbers stay out of range for the check in field_parse_raw
+            x.field = std::get<0>(c) > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)std::get<0>(c);
+            x.type = std::get<1>(c);
+            x.values = reinterpret_cast<void*>(std::get<2>(c));
+            x.length = reinterpret_cast<int32_t*>(std::get<3>(c));
+            x.status = reinterpret_cast<uint8_t*>(std::get<4>(c));
+            cs.push_back(x);
+          }
+          py::gil_scoped_release rel;
+          field_parse_raw(data, data_bytes, off, len, len_is_64, nrows, device, sep, quote, terminator, cs, stream);
+        },
+        py::arg("data"), py::arg("data_bytes"), py::arg("off"), py::arg("len"), py::arg("len_is_64"), py::arg("nrows"),
+        py::arg("device"), py::arg("cols"), py::arg("sep") = 44, py::arg("quote") = -1, py::arg("terminator") = 10,
+        py::arg("stream") = 0);
+  m.def("field_parse_launches", &field_parse_launches);
+
   // ---- native S3 data path (http_blob.cpp) --------------------------------------------------
   py::class_<BlobServer>(m, "BlobServer")
       .def(py::init<const std::string&, const std::string&, int>(), py::arg("root"), py::arg("host") = "127.0.0.1",
@@ -1020,6 +1049,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("delim_index_variant", &delim_index_variant);
   m.def("set_delim_quote_variant", &set_delim_quote_variant, py::arg("variant"));
   m.def("delim_quote_variant", &delim_quote_variant);
+  m.def("set_field_parse_variant", &set_field_parse_variant, py::arg("variant"));
+  m.def("field_parse_variant", &field_parse_variant);
   m.def("set_page_gather_chunk_variant", &set_page_gather_chunk_variant, py::arg("variant"));
   m.attr("COPY_CHUNK") = kCopyChunk;
 }

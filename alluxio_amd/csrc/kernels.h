@@ -11,6 +11,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "field_parse_host.h"
+
 namespace amdx {
 
 // One contiguous copy piece (never crosses a page boundary on the arena side).
@@ -172,6 +174,16 @@ int delim_quote_variant();
 void set_delim_index_variant(int variant, unsigned tile_shift);
 uint32_t delim_index_tile_shift();
 int delim_index_variant();
+
+// Field parse (field_parse.hip): typed columns from the rows of a batch of delimited text.
+// FieldParseArgs and the rule are in field_parse_host.h.  One launch, no workspace, no atomics; it
+// reads only bytes of rows that lie inside [data, data + data_bytes) and writes row r of every
+// column's outputs.  The launcher re-checks the scalars (sep, quote, terminator one byte each and
+// distinct, 1..32 columns, field numbers below 65536) and refuses with hipErrorInvalidValue.
+hipError_t launch_field_parse(const FieldParseArgs& a, hipStream_t stream);
+// 0 = one lane per row (a serial byte walk), 1 (default) = sixteen lanes per row over 256-byte steps.
+void set_field_parse_variant(int variant);
+int field_parse_variant();
 
 // CRC32C (Castagnoli, reflected, init/xorout 0xFFFFFFFF) of `n` equal-length pieces
 // (piece i = base + i*piece_bytes, last may be shorter: total_bytes).  `out` device array.

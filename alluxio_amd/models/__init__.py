@@ -1,5 +1,7 @@
 """Workload-facing integrations (this framework has no neural models of its own: the "models"
 it serves are training / inference input pipelines).  ``dataset`` gathers HBM-cached records
-into device batches with one kernel launch per batch."""
+into device batches with one kernel launch per batch; ``fields`` parses batches of delimited text
+into typed columns where they lie."""
 from .dataset import (DeviceBatchLoader, FixedRecordDataset, IndexedRecordDataset, RaggedBatch,  # noqa: F401
                       build_delimited_index, read_index, write_index)
+from .fields import Column, FieldColumns, parse_fields, read_delimited_columns, split_row  # noqa: F401

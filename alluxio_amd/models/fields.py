@@ -1,0 +1,319 @@
+"""Typed columns from batches of delimited text: the step after ``IndexedRecordDataset.from_delimited``
+and ``DeviceBatchLoader``, which deliver each CSV/TSV row as raw bytes.  :func:`parse_fields` splits
+the rows of a :class:`RaggedBatch` where it lies (one kernel for a device batch, a C++ loop for a
+host batch) and parses the requested fields into tensors; :func:`read_delimited_columns` does so
+for a whole file.
+
+The rule (``csrc/field_parse_host.h`` has it in full): a row is its bytes without the terminator
+(and without the ``\\r`` before a ``\\n``); a separator splits where an even number of quote bytes
+precedes it in the row; a field loses one pair of enclosing quotes, then blanks and tabs at both
+ends.  Doubled quotes inside stay as they are: a ``span`` column returns them raw and a numeric
+column calls them malformed.
+
+Column types: ``"span"`` (``start`` into the batch's flat data and ``length``), ``"int64"``,
+``"int32"``, ``"float64"``, ``"float32"``.  Status per value: 0 valid, 1 no value (field absent
+or empty), 2 malformed or out of range, 3 deferred.  The device parses a float itself only where
+one correctly rounded fp64 operation is exact (at most 19 significant digits, mantissa at most
+2^53, decimal exponent within +-22); every other well-formed float is deferred and resolved on
+the host with ``float()``, so every float64 equals ``float(text)`` bit for bit.  ``float32`` is
+that float64 converted to float32: two roundings by definition, not ``numpy.float32(text)``.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .dataset import DeviceBatchLoader, IndexedRecordDataset, RaggedBatch, build_delimited_index
+
+SPAN, INT64, INT32, FLOAT64, FLOAT32 = range(5)
+_TYPES = {"span": SPAN, "int64": INT64, "int32": INT32, "float64": FLOAT64, "float32": FLOAT32,
+          "int": INT64, "float": FLOAT64, "str": SPAN}
+_MAX_COLS = 32
+
+
+def _type_code(dtype) -> int:
+    # a name, a torch / numpy dtype (torch.int64, np.float32) or one of int, float, str
+    name = dtype.__name__ if isinstance(dtype, type) else str(dtype).replace("torch.", "")
+    try:
+        return _TYPES[name]
+    except KeyError:
+        raise ValueError(f"unknown column type {dtype!r}: one of span, int64, int32, float64, float32") from None
+
+
+def _one_byte(x, what: str) -> int:
+    b = x.encode() if isinstance(x, str) else bytes(x)
+    if len(b) != 1:
+        raise ValueError(f"the {what} must be exactly one byte, got {len(b)}")
+    return b[0]
+
+
+def _scalars(sep, quote, terminator):
+    s, t = _one_byte(sep, "separator"), _one_byte(terminator, "terminator")
+    q = -1 if quote is None else _one_byte(quote, "quote")
+    if s == t or q in (s, t):
+        raise ValueError("separator, quote and terminator must differ")
+    return s, q, t
+
+
+class Column:
+    """One parsed column: ``values`` and ``status``; a span column has ``start`` and ``length``
+    instead of ``values``."""
+
+    __slots__ = ("name", "field", "type", "values", "start", "length", "status")
+
+    def __init__(self, name, field, type_, values, length, status):
+        self.name, self.field, self.type = name, field, type_
+        self.status = status
+        if type_ == SPAN:
+            self.values, self.start, self.length = None, values, length
+        else:
+            self.values, self.start, self.length = values, None, None
+
+    def _tensors(self):
+        return (self.start, self.length, self.status) if self.type == SPAN else (self.values, self.status)
+
+    def __repr__(self):
+        kind = [k for k, v in _TYPES.items() if v == self.type][0]
+        return f"Column({self.name!r}, field={self.field}, {kind}, rows={len(self.status)})"
+
+
+class FieldColumns:
+    """The columns of one :func:`parse_fields` call, by position or by name."""
+
+    def __init__(self, columns):
+        self._cols = list(columns)
+        self._by_name = {c.name: c for c in self._cols if c.name is not None}
+
+    def __getitem__(self, key):
+        if isinstance(key, str):
+            return self._by_name[key]
+        return self._cols[key]
+
+    def __len__(self):
+        return len(self._cols)
+
+    def __iter__(self):
+        return iter(self._cols)
+
+    @property
+    def names(self):
+        return [c.name for c in self._cols]
+
+    @property
+    def rows(self) -> int:
+        return len(self._cols[0].status) if self._cols else 0
+
+    @staticmethod
+    def concat(parts):
+        """Row-wise concatenation of the results of several calls with the same columns.  Span
+        starts stay relative to each part's own batch."""
+        import torch
+        parts = list(parts)
+        cols = []
+        for j, c in enumerate(parts[0]):
+            ts = [torch.cat([p[j]._tensors()[i] for p in parts]) for i in range(len(c._tensors()))]
+            if c.type == SPAN:
+                cols.append(Column(c.name, c.field, c.type, ts[0], ts[1], ts[2]))
+            else:
+                cols.append(Column(c.name, c.field, c.type, ts[0], None, ts[1]))
+        return FieldColumns(cols)
+
+
+def _column_list(columns):
+    """[(name or None, field number, type code)]."""
+    if isinstance(columns, dict):
+        items = [(name, spec) for name, spec in columns.items()]
+    else:
+        items = [(None, spec) for spec in columns]
+    out = []
+    for name, spec in items:
+        k, dtype = spec
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"a field number is an integer, got {k!r}")
+        if k < 0:
+            raise ValueError("field numbers count from 0")
+        out.append((name, int(k), _type_code(dtype)))
+    return out
+
+
+def _alloc(type_, n, device):
+    import torch
+    dt = {SPAN: torch.int64, INT64: torch.int64, INT32: torch.int32, FLOAT64: torch.float64,
+          FLOAT32: torch.float32}[type_]
+    values = torch.empty(n, dtype=dt, device=device)
+    length = torch.empty(n, dtype=torch.int32, device=device) if type_ == SPAN else None
+    return values, length, torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def _launch(data, off, ln, specs, sep, quote, term):
+    """One native call for up to 32 columns; returns the Column objects."""
+    import torch
+    from ..ops.native import lib, native_errors
+    n = int(ln.numel())
+    dev = data.device
+    cols, raw = [], []
+    for name, k, t in specs:
+        values, length, status = _alloc(t, n, dev)
+        cols.append(Column(name, k, t, values, length, status))
+        raw.append((k, t, values.data_ptr(), length.data_ptr() if length is not None else 0, status.data_ptr()))
+    if dev.type == "cuda":
+        device, stream = dev.index if dev.index is not None else torch.cuda.current_device(), \
+            int(torch.cuda.current_stream(dev).cuda_stream)
+    else:
+        device, stream = -1, 0
+    with native_errors():
+        lib().field_parse_raw(data.data_ptr(), data.numel(), off.data_ptr(), ln.data_ptr(), ln.dtype == torch.int64, n,
+                              device, raw, sep, quote, term, stream)
+    return cols
+
+
+def _resolve(data, off, ln, cols, sep, quote, term):
+    """Deferred floats: one small readback tells whether there are any; then only the bytes of
+    those fields travel to the host, ``float()`` parses them and value and status 0 go back."""
+    import torch
+    floats = [c for c in cols if c.type in (FLOAT64, FLOAT32)]
+    if not floats or floats[0].status.numel() == 0:
+        return
+    flags = torch.stack([(c.status == 3).any() for c in floats]).cpu().tolist()
+    todo = [c for c, f in zip(floats, flags) if f]
+    for i in range(0, len(todo), _MAX_COLS):
+        group = todo[i:i + _MAX_COLS]
+        spans = _launch(data, off, ln, [(None, c.field, SPAN) for c in group], sep, quote, term)
+        flat = data.view(-1)
+        for c, s in zip(group, spans):
+            rows = torch.nonzero(c.status == 3).view(-1)
+            st, le = s.start[rows], s.length[rows].to(torch.int64)
+            ends = torch.cumsum(le, 0)
+            pos = torch.repeat_interleave(st - (ends - le), le) + torch.arange(int(ends[-1]), device=flat.device)
+            text = flat[pos].cpu().numpy().tobytes()
+            cuts = np.concatenate([[0], ends.cpu().numpy()])
+            vals = np.array([float(text[cuts[j]:cuts[j + 1]]) for j in range(len(cuts) - 1)], dtype=np.float64)
+            if c.type == FLOAT32:
+                with np.errstate(over="ignore"):
+                    vals = vals.astype(np.float32)
+            c.values[rows] = torch.from_numpy(vals).to(c.values.device)
+            c.status[rows] = 0
+
+
+def parse_fields(batch, columns, sep=",", quote=None, terminator=b"\n", resolve_deferred=True) -> FieldColumns:
+    """Parse the requested fields of every row of ``batch`` (a uint8 :class:`RaggedBatch`, packed
+    or padded, on a device or on the CPU) into tensors on the batch's device.
+
+    ``columns``: a list of ``(field number, type)`` or a dict ``name -> (field number, type)``.
+    The work runs on torch's current stream and is not waited for, except that
+    ``resolve_deferred=True`` reads one small flag back to learn whether any float was deferred;
+    ``resolve_deferred=False`` leaves such values NaN with status 3."""
+    import torch
+    data, off, ln = batch
+    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8:
+        raise ValueError("parse_fields takes a uint8 batch")
+    specs = _column_list(columns)
+    if not specs:
+        raise ValueError("at least one column is required")
+    for _, k, _t in specs:
+        if k > 65535:
+            raise ValueError("field numbers above 65535 are not supported")
+    s, q, t = _scalars(sep, quote, terminator)
+    dev = data.device
+    data = data if data.is_contiguous() else data.contiguous()
+    n = int(ln.numel())
+    off = off.to(device=dev, dtype=torch.int64)[:n].contiguous()
+    if ln.dtype not in (torch.int32, torch.int64):
+        ln = ln.to(torch.int64)
+    ln = ln.to(dev).contiguous()
+    cols = []
+    for i in range(0, len(specs), _MAX_COLS):
+        cols += _launch(data, off, ln, specs[i:i + _MAX_COLS], s, q, t)
+    if resolve_deferred:
+        _resolve(data, off, ln, cols, s, q, t)
+    return FieldColumns(cols)
+
+
+def split_row(row: bytes, sep=",", quote=None, terminator=b"\n") -> list:
+    """The contents of the fields of one row, by the rule above, on the host."""
+    s, q, t = _scalars(sep, quote, terminator)
+    if row.endswith(bytes([t])):
+        row = row[:-1]
+        if t == 0x0A and row.endswith(b"\r"):
+            row = row[:-1]
+    fields, start, inside = [], 0, False
+    for i, c in enumerate(row):
+        if c == q:
+            inside = not inside
+        elif c == s and not inside:
+            fields.append(row[start:i])
+            start = i + 1
+    fields.append(row[start:])
+    out = []
+    for f in fields:
+        if q >= 0 and len(f) >= 2 and f[0] == q and f[-1] == q:
+            f = f[1:-1]
+        out.append(f.strip(b" \t"))
+    return out
+
+
+def read_delimited_columns(fs, path: str, columns, sep=",", quote=None, delimiter=b"\n", header: bool = False,
+                           skip_rows: int = 0, batch_size: int = 65536, device=None, device_plan="auto") -> FieldColumns:
+    """The requested columns of a whole delimited text file, concatenated over an unshuffled
+    :class:`DeviceBatchLoader` of ``batch_size`` rows.  The ``start`` of a span column is an offset
+    into the file here (into the batch's data in :func:`parse_fields`).
+
+    ``header=True``: the first record is read through the client stream and split by the same rule
+    on the host; ``columns`` may then name a field by its header text instead of its number (an
+    unknown name is a ``KeyError``, a header with the same name twice a ``ValueError``), and the
+    header row is dropped.  ``skip_rows`` drops further leading records."""
+    if skip_rows < 0:
+        raise ValueError("skip_rows counts rows")
+    s, q, t = _scalars(sep, quote, delimiter)
+    index = build_delimited_index(fs, path, delimiter, quote=quote, device_plan=device_plan)
+    named = isinstance(columns, dict)
+    items = list(columns.items()) if named else [(None, spec) for spec in columns]
+    drop = int(skip_rows)
+    if header:
+        if len(index) < 2:
+            raise ValueError(f"{path}: no header row")
+        with fs.open_file(path) as f:
+            buf = np.empty(int(index[1]), dtype=np.uint8)
+            got = 0
+            while got < len(buf):
+                k = f.readinto(buf[got:])
+                if k <= 0:
+                    break
+                got += k
+        names = [x.decode("utf-8", "replace") for x in split_row(buf[:got].tobytes(), sep, quote, delimiter)]
+        if len(set(names)) != len(names):
+            raise ValueError(f"{path}: the header names a column twice")
+        where = {nm: i for i, nm in enumerate(names)}
+        resolved = []
+        for name, (k, dtype) in items:
+            if isinstance(k, str):
+                if k not in where:
+                    raise KeyError(k)
+                k = where[k]
+            resolved.append((name, (k, dtype)))
+        items = resolved
+        drop += 1
+    elif any(isinstance(k, str) for _, (k, _d) in items):
+        raise ValueError("columns are named by header text only with header=True")
+    spec = dict(items) if named else [sp for _, sp in items]
+    index = index[min(drop, len(index) - 1):]
+    ds = IndexedRecordDataset(fs, path, index=index, device=device)
+    parts = []
+    with DeviceBatchLoader(ds, batch_size=batch_size, device=device, align=1, device_plan=device_plan) as dl:
+        import torch
+        file_off = torch.from_numpy(np.ascontiguousarray(index[:-1])).to(dl.device)
+        done = 0
+        for batch in dl:
+            got = parse_fields(batch, spec, sep, quote, delimiter)
+            n = got.rows
+            for c in got:
+                if c.type == SPAN:                      # batch offsets -> file offsets
+                    rel = c.start - batch.offsets[:n].to(torch.int64) + file_off[done:done + n]
+                    c.start = torch.where(c.status == 0, rel, torch.zeros_like(rel))
+            done += n
+            parts.append(got)
+        if not parts:
+            empty = RaggedBatch(torch.empty(0, dtype=torch.uint8, device=dl.device),
+                                torch.zeros(1, dtype=torch.int64, device=dl.device),
+                                torch.empty(0, dtype=torch.int64, device=dl.device))
+            parts.append(parse_fields(empty, spec, sep, quote, delimiter))
+    return FieldColumns.concat(parts)
