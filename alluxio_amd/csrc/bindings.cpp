@@ -1038,10 +1038,22 @@ PYBIND11_MODULE(_C, m) {
   m.def("evict_select_device", &evict_select_device);
   m.def("page_alloc_device", &page_alloc_device);
   m.def("set_copy_variant", &set_copy_variant, py::arg("variant"), py::arg("grid_cap") = 0);
+  m.def("copy_variant", [] {
+    int v = 0;
+    unsigned cap = 0;
+    copy_variant(&v, &cap);
+    return py::make_tuple(v, cap);
+  });
   m.def("set_crc_variant", &set_crc_variant, py::arg("variant"));
   m.def("set_lz4_decode_variant", &set_lz4_decode_variant, py::arg("variant"));
   m.def("set_lz4_encode_variant", &set_lz4_encode_variant, py::arg("variant"));
   m.def("set_seq_read_variant", &set_seq_read_variant, py::arg("variant"), py::arg("grid_cap") = 0);
+  m.def("seq_read_variant", [] {
+    int v = 0;
+    unsigned cap = 0;
+    seq_read_variant(&v, &cap);
+    return py::make_tuple(v, cap);
+  });
   m.def("set_ragged_gather_variant", &set_ragged_gather_variant, py::arg("variant"), py::arg("chunk_shift") = 0);
   m.def("ragged_gather_chunk_shift", &ragged_gather_chunk_shift);
   m.def("set_delim_index_variant", &set_delim_index_variant, py::arg("variant"), py::arg("tile_shift") = 0);

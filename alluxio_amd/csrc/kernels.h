@@ -30,8 +30,10 @@ constexpr uint64_t kCopyChunk = 256 * 1024;
 // ceil(bytes / kCopyChunk).  Grid is capped and grid-strided.
 hipError_t launch_batched_copy(const CopySeg* segs, int nseg, uint64_t total_chunks,
                                hipStream_t stream);
-// Select the copy kernel variant (cache policy / unroll) and grid cap; used for A/B tuning.
+// Select the copy kernel variant (cache policy / unroll) and grid cap (0 keeps it); used for A/B
+// tuning.  The getter returns both as they stand.
 void set_copy_variant(int variant, unsigned grid_cap);
+void copy_variant(int* variant, unsigned* grid_cap);
 
 // Device-cursor sequential multi-stream read (StressWorkerBench shape, K1 without per-read
 // descriptors).  S streams each issue `depth` consecutive read(buf) calls per launch over one
@@ -58,8 +60,11 @@ struct SeqReadArgs {
 };
 constexpr uint32_t kSeqReadMaxStreams = 8192;
 hipError_t launch_seq_read(const SeqReadArgs& a, hipStream_t stream);
-// A/B switch for the sequential-read kernel (bit0: nontemporal ring stores, bit1: unroll 16).
+// A/B switch for the sequential-read kernel (bit0: nontemporal ring stores, bit1: unroll 16,
+// bit2: nontemporal loads; -1: the launcher chooses by the launch's footprint).  grid_cap 0 keeps
+// the cap.  The getter returns both as they stand, so a caller can put them back.
 void set_seq_read_variant(int variant, unsigned grid_cap);
+void seq_read_variant(int* variant, unsigned* grid_cap);
 
 // Ragged gather (ragged_gather.hip): `batch` variable-length records, picked by `idx` from a
 // device-resident record index (RaggedRec: virtual byte address and length), are read through a
@@ -345,6 +350,8 @@ hipError_t launch_page_lookup_gather(const PageGatherArgs& a, hipStream_t stream
 void set_page_gather_small_max(uint64_t bytes);
 void set_page_gather_wave_variant(int variant);
 void set_page_gather_chunk_variant(int v);
+// The three settings above as they stand: small_max, wave variant, chunk variant.
+void page_gather_config(uint64_t* small_max, int* wave_variant, int* chunk_variant);
 // Apply table updates (idx, entry) pairs uploaded by the host mirror.
 hipError_t launch_page_table_update(PageTableEntry* table, const uint64_t* idx,
                                     const PageTableEntry* entries, uint32_t n, hipStream_t stream);

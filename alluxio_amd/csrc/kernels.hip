@@ -99,6 +99,10 @@ void set_copy_variant(int variant, unsigned grid_cap) {
   g_copy_variant = variant;
   if (grid_cap) g_copy_grid_cap = grid_cap;
 }
+void copy_variant(int* variant, unsigned* grid_cap) {
+  *variant = g_copy_variant;
+  *grid_cap = g_copy_grid_cap;
+}
 
 hipError_t launch_batched_copy(const CopySeg* segs, int nseg, uint64_t total_chunks,
                                hipStream_t stream) {
@@ -214,6 +218,10 @@ static unsigned g_seq_grid_cap = 8192;
 void set_seq_read_variant(int variant, unsigned grid_cap) {
   g_seq_variant = variant;
   if (grid_cap) g_seq_grid_cap = grid_cap;
+}
+void seq_read_variant(int* variant, unsigned* grid_cap) {
+  *variant = g_seq_variant;
+  *grid_cap = g_seq_grid_cap;
 }
 
 static inline bool is_pow2(uint64_t x) { return x && !(x & (x - 1)); }
@@ -2935,6 +2943,11 @@ void set_page_gather_wave_variant(int v) { g_pg_wave_variant = v; }
 // 2 MiB pages equal within noise; profiles/r3_page_gather_ntload.jsonl)
 static int g_pg_chunk_variant = -1;
 void set_page_gather_chunk_variant(int v) { g_pg_chunk_variant = v; }
+void page_gather_config(uint64_t* small_max, int* wave_variant, int* chunk_variant) {
+  *small_max = g_pg_small_max;
+  *wave_variant = g_pg_wave_variant;
+  *chunk_variant = g_pg_chunk_variant;
+}
 
 __device__ __forceinline__ void pg_resolve(const PageGatherArgs& a, uint64_t key, uint64_t h,
                                            PageTableEntry e, int lane, int32_t& slot, uint32_t& len) {

@@ -77,6 +77,13 @@ inline void bind_page_cache(pybind11::module_& m) {
   m.attr("PAGE_KEY_EMPTY") = kPageKeyEmpty;
   m.def("set_page_gather_small_max", &set_page_gather_small_max, py::arg("bytes"));
   m.def("set_page_gather_wave_variant", &set_page_gather_wave_variant, py::arg("variant"));
+  m.def("page_gather_config", [] {
+    uint64_t small_max = 0;
+    int wave = 0, chunk = 0;
+    page_gather_config(&small_max, &wave, &chunk);
+    return py::make_tuple(small_max, wave, chunk);
+  });
+  m.def("page_key_hash", [](uint64_t key) { return page_key_hash(key); }, py::arg("key"));
 }
 
 }  // namespace amdx

@@ -1,9 +1,11 @@
 """Numerics of the CDNA4 kernels against host references (gpu-marked).
 
-Each HIP kernel is compared with a plain host implementation of the same op: byte-exact copy,
-CRC32C vs the slicing-by-8 software CRC (itself pinned to the standard check value), LZ4 vs the
-host codec (decode of host-encoded data, host-decode of device-encoded data), eviction selection
-vs a sorted host reference.
+Each HIP kernel is compared with a plain host implementation of the same op: the batched copy
+at its default variant, on the bytes inside its segments only (every variant, every alignment
+phase and the bytes around the segments are in test_copy_kernels.py), CRC32C vs the
+slicing-by-8 software CRC (itself pinned to the standard check value), LZ4 vs the host codec
+(decode of host-encoded data, host-decode of device-encoded data), eviction selection vs a
+sorted host reference.
 """
 import os
 
