@@ -38,10 +38,10 @@ namespace {
     if (_e != hipSuccess) throw StoreError(kErrHip, std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
 
-struct DevBuf {
+struct ScratchBuf {
   void* p = nullptr;
-  explicit DevBuf(size_t n) { HIP_CHECK(hipMalloc(&p, n ? n : 1)); }
-  ~DevBuf() { if (p) (void)hipFree(p); }
+  explicit ScratchBuf(size_t n) { HIP_CHECK(hipMalloc(&p, n ? n : 1)); }
+  ~ScratchBuf() { if (p) (void)hipFree(p); }
 };
 
 // The vector becomes the numpy array's storage (no copy).
@@ -63,7 +63,7 @@ std::vector<uint32_t> crc32c_device(uint64_t ptr, uint64_t len, uint64_t piece, 
   std::vector<uint32_t> out(np);
   if (!np) return out;
   const uint64_t sw = crc32c_scratch_words(len, piece);
-  DevBuf d((np + sw) * 4);
+  ScratchBuf d((np + sw) * 4);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   HIP_CHECK(launch_crc32c_pieces(reinterpret_cast<const uint8_t*>(ptr), len, piece, (uint32_t*)d.p,
                                  (uint32_t*)d.p + np, sw, st));
@@ -82,8 +82,8 @@ std::vector<uint32_t> crc32c_device_pages(uint64_t base, const std::vector<int64
   std::vector<uint32_t> out(np);
   if (!np) return out;
   const uint64_t sw = crc32c_pages_scratch_words(len, page_bytes);
-  DevBuf d((np + sw) * 4);
-  DevBuf idx(np * sizeof(int64_t));
+  ScratchBuf d((np + sw) * 4);
+  ScratchBuf idx(np * sizeof(int64_t));
   HIP_CHECK(hipMemcpy(idx.p, pages.data(), np * sizeof(int64_t), hipMemcpyHostToDevice));
   HIP_CHECK(launch_crc32c_pages(reinterpret_cast<const uint8_t*>(base), (const int64_t*)idx.p, len, page_bytes,
                                 (uint32_t*)d.p, (uint32_t*)d.p + np, sw, 0));
@@ -104,7 +104,7 @@ std::vector<int32_t> lz4_device(const std::vector<std::tuple<uint64_t, uint64_t,
     h[i].src_bytes = std::get<2>(chunks[i]);
     h[i].dst_capacity = std::get<3>(chunks[i]);
   }
-  DevBuf dch(sizeof(Lz4Chunk) * n), dsz(sizeof(int32_t) * n);
+  ScratchBuf dch(sizeof(Lz4Chunk) * n), dsz(sizeof(int32_t) * n);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   HIP_CHECK(hipMemcpyAsync(dch.p, h.data(), sizeof(Lz4Chunk) * n, hipMemcpyHostToDevice, st));
   if (compress) HIP_CHECK(launch_lz4_compress((Lz4Chunk*)dch.p, n, (int32_t*)dsz.p, st));
@@ -123,7 +123,7 @@ double lz4_device_kernel_ms(const std::vector<std::tuple<uint64_t, uint64_t, uin
   std::vector<Lz4Chunk> h(n);
   for (int i = 0; i < n; ++i)
     h[i] = Lz4Chunk{std::get<0>(chunks[i]), std::get<1>(chunks[i]), std::get<2>(chunks[i]), std::get<3>(chunks[i])};
-  DevBuf dch(sizeof(Lz4Chunk) * n), dsz(sizeof(int32_t) * n);
+  ScratchBuf dch(sizeof(Lz4Chunk) * n), dsz(sizeof(int32_t) * n);
   HIP_CHECK(hipMemcpy(dch.p, h.data(), sizeof(Lz4Chunk) * n, hipMemcpyHostToDevice));
   hipEvent_t a, b;
   HIP_CHECK(hipEventCreate(&a));
@@ -186,7 +186,7 @@ py::tuple evict_select_device(const std::vector<float>& crf, const std::vector<u
     py::gil_scoped_release rel;
     std::vector<int32_t> dir(n);
     for (size_t i = 0; i < n; ++i) dir[i] = evictable[i] ? 0 : -1;
-    DevBuf dc(n * 4 + 4), dl(n * 8 + 8), db(n * 8 + 8), dd(n * 4 + 4), dk(n * 4 + 4), dout(n * 4 + 4),
+    ScratchBuf dc(n * 4 + 4), dl(n * 8 + 8), db(n * 8 + 8), dd(n * 4 + 4), dk(n * 4 + 4), dout(n * 4 + 4),
         dctl(sizeof(EvictCtl));
     HIP_CHECK(hipMemcpy(dc.p, crf.data(), n * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(dl.p, last.data(), n * 8, hipMemcpyHostToDevice));
@@ -223,7 +223,7 @@ py::tuple page_alloc_device(const std::vector<uint64_t>& bits, uint32_t want) {
   std::vector<uint64_t> after(nw);
   {
     py::gil_scoped_release rel;
-    DevBuf db((size_t)nw * 8 + 8), dp((size_t)page_alloc_partials(nw) * 4 + 4), dout((size_t)want * 8 + 8), dc(8);
+    ScratchBuf db((size_t)nw * 8 + 8), dp((size_t)page_alloc_partials(nw) * 4 + 4), dout((size_t)want * 8 + 8), dc(8);
     if (nw) HIP_CHECK(hipMemcpy(db.p, bits.data(), (size_t)nw * 8, hipMemcpyHostToDevice));
     HIP_CHECK(launch_page_alloc((uint64_t*)db.p, nw, want, (uint32_t*)dp.p, (int64_t*)dout.p, (uint32_t*)dc.p,
                                 nullptr));

@@ -12,17 +12,10 @@
 #include <sstream>
 
 #include "cpu_codecs.h"
+#include "paged_view.h"
 #include "trace.h"
 
 namespace amdx {
-
-#define HIP_OK(expr)                                                                       \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess)                                                                  \
-      throw StoreError(kErrHip, std::string("HIP error: ") + hipGetErrorString(_e) + " at " \
-                                    + #expr);                                              \
-  } while (0)
 
 static inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 
@@ -81,19 +74,19 @@ BlockStore::BlockStore(const std::vector<DirSpec>& dirs, int annotator, int allo
   dir_ev_bytes_.assign(dirs_.size(), 0);
   if (has_device_) {
     set_device();
-    HIP_OK(hipStreamCreateWithFlags(&internal_stream_, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i) HIP_OK(hipEventCreateWithFlags(&upd_ev_[i], hipEventDisableTiming));
-    HIP_OK(hipHostMalloc((void**)&h_ctl_, sizeof(EvictCtl), hipHostMallocDefault));
-    HIP_OK(hipMalloc((void**)&d_ctl_, sizeof(EvictCtl)));
-    HIP_OK(hipHostMalloc((void**)&h_claimed_, sizeof(uint32_t), hipHostMallocDefault));
-    HIP_OK(hipMalloc((void**)&d_claimed_, sizeof(uint32_t)));
-    HIP_OK(hipHostMalloc((void**)&host_ring_, sizeof(CopySeg) * kRing * kRingSegs, hipHostMallocDefault));
-    HIP_OK(hipMalloc((void**)&dev_ring_, sizeof(CopySeg) * kRing * kRingSegs));
-    for (int i = 0; i < kRing; ++i) HIP_OK(hipEventCreateWithFlags(&ring_ev_[i], hipEventDisableTiming));
+    AMDX_HIP(hipStreamCreateWithFlags(&internal_stream_, hipStreamNonBlocking));
+    for (int i = 0; i < 2; ++i) AMDX_HIP(hipEventCreateWithFlags(&upd_ev_[i], hipEventDisableTiming));
+    AMDX_HIP(hipHostMalloc((void**)&h_ctl_, sizeof(EvictCtl), hipHostMallocDefault));
+    AMDX_HIP(hipMalloc((void**)&d_ctl_, sizeof(EvictCtl)));
+    AMDX_HIP(hipHostMalloc((void**)&h_claimed_, sizeof(uint32_t), hipHostMallocDefault));
+    AMDX_HIP(hipMalloc((void**)&d_claimed_, sizeof(uint32_t)));
+    AMDX_HIP(hipHostMalloc((void**)&host_ring_, sizeof(CopySeg) * kRing * kRingSegs, hipHostMallocDefault));
+    AMDX_HIP(hipMalloc((void**)&dev_ring_, sizeof(CopySeg) * kRing * kRingSegs));
+    for (int i = 0; i < kRing; ++i) AMDX_HIP(hipEventCreateWithFlags(&ring_ev_[i], hipEventDisableTiming));
     for (auto& d : dirs_) {
       if (d->spec.kind != DirKind::kDevice || d->free_bits.empty()) continue;
-      HIP_OK(hipMalloc((void**)&d->mag_bits, d->free_bits.size() * 8));
-      HIP_OK(hipMemset(d->mag_bits, 0, d->free_bits.size() * 8));
+      AMDX_HIP(hipMalloc((void**)&d->mag_bits, d->free_bits.size() * 8));
+      AMDX_HIP(hipMemset(d->mag_bits, 0, d->free_bits.size() * 8));
     }
     const char* mk = std::getenv("ALLUXIO_MOVE_COPY_KERNEL");
     const bool mapped_moves = !(mk && mk[0] == '0');
@@ -125,11 +118,11 @@ hipStream_t thread_stream_on(int device) {
     if (kv.first == device) return kv.second;
   int prev = -1;
   (void)hipGetDevice(&prev);
-  if (prev != device) HIP_OK(hipSetDevice(device));
+  if (prev != device) AMDX_HIP(hipSetDevice(device));
   hipStream_t st = nullptr;
   const hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
   if (prev != device && prev >= 0) (void)hipSetDevice(prev);
-  HIP_OK(e);
+  AMDX_HIP(e);
   tl.by_device.emplace_back(device, st);
   g_thread_streams.fetch_add(1, std::memory_order_relaxed);
   return st;
@@ -418,14 +411,14 @@ void BlockStore::mag_refill(StorageDir& d, int64_t want) {
     if (d.mag_upd) hipFree(d.mag_upd);
     d.mag_upd = nullptr;
     const size_t cap = std::max<size_t>(upd.size(), 1024);
-    HIP_OK(hipMalloc((void**)&d.mag_upd, cap * 8));
+    AMDX_HIP(hipMalloc((void**)&d.mag_upd, cap * 8));
     d.mag_upd_cap = cap;
   }
   // on the internal stream, completed before returning: the (pageable) update list is consumed
   // and any stream claiming afterwards sees the pages
-  HIP_OK(hipMemcpyAsync(d.mag_upd, upd.data(), upd.size() * 8, hipMemcpyHostToDevice, internal_stream_));
-  HIP_OK(launch_mag_fill(d.mag_bits, (uint32_t)nwords, d.mag_upd, (uint32_t)n, internal_stream_));
-  HIP_OK(hipStreamSynchronize(internal_stream_));
+  AMDX_HIP(hipMemcpyAsync(d.mag_upd, upd.data(), upd.size() * 8, hipMemcpyHostToDevice, internal_stream_));
+  AMDX_HIP(launch_mag_fill(d.mag_bits, (uint32_t)nwords, d.mag_upd, (uint32_t)n, internal_stream_));
+  AMDX_HIP(hipStreamSynchronize(internal_stream_));
   d.mag_pages += moved;
   ++stats_.mag_refills;
   stats_.mag_refill_pages += moved;
@@ -447,7 +440,7 @@ int64_t BlockStore::mag_drain(StorageDir& d) {
   if (!d.mag_bits) return 0;
   const uint32_t nwords = (uint32_t)d.free_bits.size();
   uint64_t* dout = nullptr;
-  HIP_OK(hipMalloc((void**)&dout, (size_t)nwords * 8));
+  AMDX_HIP(hipMalloc((void**)&dout, (size_t)nwords * 8));
   std::vector<uint64_t> out(nwords);
   hipError_t e = launch_mag_drain(d.mag_bits, nwords, dout, internal_stream_);
   if (e == hipSuccess) e = hipMemcpyAsync(out.data(), dout, (size_t)nwords * 8, hipMemcpyDeviceToHost, internal_stream_);
@@ -627,7 +620,7 @@ void BlockStore::write(int64_t session, int64_t block_id, uint64_t offset, uint6
   }
   plan_block_range(snapshot, offset, len, src, src_kind, /*to_block=*/true, dev_segs, st);
   if (!dev_segs.empty()) copy_segments(dev_segs, st);
-  if (sync && has_device_) HIP_OK(hipStreamSynchronize(st));
+  if (sync && has_device_) AMDX_HIP(hipStreamSynchronize(st));
 }
 
 void BlockStore::commit_block(int64_t session, int64_t block_id, bool pin) {
@@ -759,7 +752,7 @@ int BlockStore::move_block(int64_t session, int64_t block_id, int dst_tier, cons
   try {
     copy_block_storage(src_snap, nb, dev_segs, st);
     if (!dev_segs.empty()) copy_segments(dev_segs, st);
-    if (has_device_) HIP_OK(hipStreamSynchronize(st));
+    if (has_device_) AMDX_HIP(hipStreamSynchronize(st));
   } catch (...) {
     lk.lock();
     release_storage(nb);
@@ -816,7 +809,7 @@ void BlockStore::copy_block_storage(const BlockMeta& src_snap, const BlockMeta& 
   std::vector<uint8_t> bounce(len);
   std::vector<CopySeg> none;
   plan_block_range(src_snap, 0, len, (uint64_t)bounce.data(), (int)MemKind::kHost, false, none, st);
-  if (has_device_) HIP_OK(hipStreamSynchronize(st));
+  if (has_device_) AMDX_HIP(hipStreamSynchronize(st));
   if (dd.spec.kind == DirKind::kFile) {
     std::string fin;
     file_path(dd, nb.id, fin);
@@ -827,7 +820,7 @@ void BlockStore::copy_block_storage(const BlockMeta& src_snap, const BlockMeta& 
     if (w != (ssize_t)len) throw StoreError(kErrIo, "short write to " + fin);
   } else {
     plan_block_range(nb, 0, len, (uint64_t)bounce.data(), (int)MemKind::kHost, true, none, st);
-    if (has_device_) HIP_OK(hipStreamSynchronize(st));
+    if (has_device_) AMDX_HIP(hipStreamSynchronize(st));
   }
 }
 
@@ -914,7 +907,7 @@ std::vector<int64_t> BlockStore::move_blocks_locked(std::unique_lock<std::mutex>
   try {
     for (auto& j : jobs) copy_block_storage(j.snap, j.nb, dev_segs, st);
     if (!dev_segs.empty()) copy_segments(dev_segs, st);
-    if (has_device_) HIP_OK(hipStreamSynchronize(st));   // one sync for the whole batch
+    if (has_device_) AMDX_HIP(hipStreamSynchronize(st));   // one sync for the whole batch
   } catch (...) {
     err = std::current_exception();
   }
@@ -1115,7 +1108,7 @@ void BlockStore::plan_block_range(const BlockMeta& b, uint64_t offset, uint64_t 
       host = bounce.data();
       if (to_block) {
         hipError_t e = hipMemcpy(host, reinterpret_cast<void*>(ext), len, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { ::close(fd); HIP_OK(e); }
+        if (e != hipSuccess) { ::close(fd); AMDX_HIP(e); }
       }
     }
     uint64_t done = 0;
@@ -1126,7 +1119,7 @@ void BlockStore::plan_block_range(const BlockMeta& b, uint64_t offset, uint64_t 
       done += (uint64_t)r;
     }
     ::close(fd);
-    if (ext_dev && !to_block) HIP_OK(hipMemcpy(reinterpret_cast<void*>(ext), host, len, hipMemcpyHostToDevice));
+    if (ext_dev && !to_block) AMDX_HIP(hipMemcpy(reinterpret_cast<void*>(ext), host, len, hipMemcpyHostToDevice));
     return;
   }
   const uint64_t ps = d.spec.page_size;
@@ -1158,7 +1151,7 @@ void BlockStore::plan_block_range(const BlockMeta& b, uint64_t offset, uint64_t 
     } else {
       const hipMemcpyKind kind = to_block ? (arena_dev ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost)
                                           : (arena_dev ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice);
-      HIP_OK(hipMemcpyAsync(reinterpret_cast<void*>(dst), reinterpret_cast<const void*>(src), n, kind, stream));
+      AMDX_HIP(hipMemcpyAsync(reinterpret_cast<void*>(dst), reinterpret_cast<const void*>(src), n, kind, stream));
     }
     pos += n;
     done += n;
@@ -1172,7 +1165,7 @@ void BlockStore::copy_segments(std::vector<CopySeg>& segs, hipStream_t stream) {
     const size_t cnt = std::min<size_t>(segs.size() - base, kRingSegs);
     const int slot = ring_pos_;
     ring_pos_ = (ring_pos_ + 1) % kRing;
-    HIP_OK(hipEventSynchronize(ring_ev_[slot]));
+    AMDX_HIP(hipEventSynchronize(ring_ev_[slot]));
     CopySeg* h = host_ring_ + (size_t)slot * kRingSegs;
     CopySeg* dv = dev_ring_ + (size_t)slot * kRingSegs;
     uint64_t chunks = 0;
@@ -1181,9 +1174,9 @@ void BlockStore::copy_segments(std::vector<CopySeg>& segs, hipStream_t stream) {
       h[i].chunk0 = chunks;
       chunks += ceil_div(h[i].bytes, kCopyChunk);
     }
-    HIP_OK(hipMemcpyAsync(dv, h, sizeof(CopySeg) * cnt, hipMemcpyHostToDevice, stream));
-    HIP_OK(launch_batched_copy(dv, (int)cnt, chunks, stream));
-    HIP_OK(hipEventRecord(ring_ev_[slot], stream));
+    AMDX_HIP(hipMemcpyAsync(dv, h, sizeof(CopySeg) * cnt, hipMemcpyHostToDevice, stream));
+    AMDX_HIP(launch_batched_copy(dv, (int)cnt, chunks, stream));
+    AMDX_HIP(hipEventRecord(ring_ev_[slot], stream));
     base += cnt;
   }
   segs.clear();
@@ -1215,7 +1208,7 @@ void BlockStore::read_batch(const std::vector<ReadReq>& reqs, uint64_t stream, b
     plan_block_range(snaps[i], reqs[i].offset, reqs[i].length, reqs[i].dst, reqs[i].dst_kind, false,
                      dev_segs, st);
   if (!dev_segs.empty()) copy_segments(dev_segs, st);
-  if (sync && has_device_) HIP_OK(hipStreamSynchronize(st));
+  if (sync && has_device_) AMDX_HIP(hipStreamSynchronize(st));
 }
 
 std::vector<uint32_t> BlockStore::checksum(int64_t block_id, uint64_t piece_bytes) {
@@ -1251,7 +1244,7 @@ std::vector<uint32_t> BlockStore::checksum(int64_t block_id, uint64_t piece_byte
   if (crc_cap_ < need) {
     if (crc_dev_) hipFree(crc_dev_);
     crc_dev_ = nullptr;
-    HIP_OK(hipMalloc((void**)&crc_dev_, need * sizeof(uint32_t)));
+    AMDX_HIP(hipMalloc((void**)&crc_dev_, need * sizeof(uint32_t)));
     crc_cap_ = need;
   }
   // contiguous page runs, each a whole number of pieces
@@ -1264,14 +1257,14 @@ std::vector<uint32_t> BlockStore::checksum(int64_t block_id, uint64_t piece_byte
     const uint8_t* base = reinterpret_cast<const uint8_t*>(d.spec.base + (uint64_t)snap.pages[i] * ps);
     const uint64_t np = ceil_div(run, piece_bytes);
     uint32_t* scratch = crc_dev_ + out.size();
-    HIP_OK(launch_crc32c_pieces(base, run, piece_bytes, crc_dev_ + piece_idx, scratch,
+    AMDX_HIP(launch_crc32c_pieces(base, run, piece_bytes, crc_dev_ + piece_idx, scratch,
                                 crc_cap_ - out.size(), internal_stream_));
     piece_idx += np;
     off += run;
     i = j;
   }
-  HIP_OK(hipMemcpyAsync(out.data(), crc_dev_, out.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, internal_stream_));
-  HIP_OK(hipStreamSynchronize(internal_stream_));
+  AMDX_HIP(hipMemcpyAsync(out.data(), crc_dev_, out.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, internal_stream_));
+  AMDX_HIP(hipStreamSynchronize(internal_stream_));
   return out;
 }
 
@@ -1309,15 +1302,15 @@ size_t BlockStore::checksum_async(int64_t block_id, hipStream_t stream, uint32_t
       int64_t* host_idx = reinterpret_cast<int64_t*>(host_out + idx_word);
       for (size_t k = 0; k < np; ++k) host_idx[k] = snap.pages[k];
       int64_t* dev_idx = reinterpret_cast<int64_t*>(dev_buf + idx_word);
-      HIP_OK(hipMemcpyAsync(dev_idx, host_idx, np * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+      AMDX_HIP(hipMemcpyAsync(dev_idx, host_idx, np * sizeof(int64_t), hipMemcpyHostToDevice, stream));
       const hipError_t e = launch_crc32c_pages(reinterpret_cast<const uint8_t*>(d.spec.base), dev_idx, len, ps,
                                                dev_buf, dev_buf + np, scratch, stream);
       if (e == hipSuccess) {
-        HIP_OK(hipMemcpyAsync(host_out, dev_buf, np * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        AMDX_HIP(hipMemcpyAsync(host_out, dev_buf, np * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         if (page_size_out) *page_size_out = ps;
         return np;
       }
-      if (e != hipErrorNotSupported) HIP_OK(e);
+      if (e != hipErrorNotSupported) AMDX_HIP(e);
     }
   }
   uint64_t off = 0;
@@ -1327,12 +1320,12 @@ size_t BlockStore::checksum_async(int64_t block_id, hipStream_t stream, uint32_t
     while (j < snap.pages.size() && snap.pages[j] == snap.pages[j - 1] + 1) ++j;
     const uint64_t run = std::min<uint64_t>((j - i) * ps, len - off);
     const uint8_t* base = reinterpret_cast<const uint8_t*>(d.spec.base + (uint64_t)snap.pages[i] * ps);
-    HIP_OK(launch_crc32c_pieces(base, run, ps, dev_buf + piece_idx, dev_buf + np, dev_words - np, stream));
+    AMDX_HIP(launch_crc32c_pieces(base, run, ps, dev_buf + piece_idx, dev_buf + np, dev_words - np, stream));
     piece_idx += (size_t)ceil_div(run, ps);
     off += run;
     i = j;
   }
-  HIP_OK(hipMemcpyAsync(host_out, dev_buf, np * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  AMDX_HIP(hipMemcpyAsync(host_out, dev_buf, np * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
   if (page_size_out) *page_size_out = ps;
   return np;
 }
@@ -1374,18 +1367,18 @@ std::vector<std::pair<uint64_t, std::vector<uint32_t>>> BlockStore::checksum_blo
     if (crc_cap_ < need) {
       if (crc_dev_) hipFree(crc_dev_);
       crc_dev_ = nullptr;
-      HIP_OK(hipMalloc((void**)&crc_dev_, need * sizeof(uint32_t)));
+      AMDX_HIP(hipMalloc((void**)&crc_dev_, need * sizeof(uint32_t)));
       crc_cap_ = need;
     }
     uint64_t* dptr = reinterpret_cast<uint64_t*>(crc_dev_);
     uint32_t* dlen = crc_dev_ + 2 * n;
     uint32_t* dout = crc_dev_ + 3 * n;
-    HIP_OK(hipMemcpyAsync(dptr, ptrs.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, internal_stream_));
-    HIP_OK(hipMemcpyAsync(dlen, lens.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, internal_stream_));
-    HIP_OK(launch_crc32c_gather(dptr, dlen, n, dout, internal_stream_));
+    AMDX_HIP(hipMemcpyAsync(dptr, ptrs.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, internal_stream_));
+    AMDX_HIP(hipMemcpyAsync(dlen, lens.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, internal_stream_));
+    AMDX_HIP(launch_crc32c_gather(dptr, dlen, n, dout, internal_stream_));
     std::vector<uint32_t> res(n);
-    HIP_OK(hipMemcpyAsync(res.data(), dout, n * sizeof(uint32_t), hipMemcpyDeviceToHost, internal_stream_));
-    HIP_OK(hipStreamSynchronize(internal_stream_));
+    AMDX_HIP(hipMemcpyAsync(res.data(), dout, n * sizeof(uint32_t), hipMemcpyDeviceToHost, internal_stream_));
+    AMDX_HIP(hipStreamSynchronize(internal_stream_));
     for (auto& [i, first] : where)
       std::copy(res.begin() + first, res.begin() + first + out[i].second.size(), out[i].second.begin());
   }
@@ -1431,11 +1424,11 @@ void BlockStore::fill_pattern(int64_t session, int64_t block_id, uint64_t length
     while (j < snap.pages.size() && snap.pages[j] == snap.pages[j - 1] + 1) ++j;
     const uint64_t run = std::min<uint64_t>((j - i) * ps, length - off);
     uint8_t* base = reinterpret_cast<uint8_t*>(d.spec.base + (uint64_t)snap.pages[i] * ps);
-    HIP_OK(launch_fill_pattern(base, run, seed, off >> 3, internal_stream_));
+    AMDX_HIP(launch_fill_pattern(base, run, seed, off >> 3, internal_stream_));
     off += run;
     i = j;
   }
-  HIP_OK(hipStreamSynchronize(internal_stream_));
+  AMDX_HIP(hipStreamSynchronize(internal_stream_));
 }
 
 // -------------------------------------------------------------------------------------------
@@ -1484,25 +1477,25 @@ void BlockStore::ensure_dev_slots_locked(size_t n) {
     uint64_t *last, *fb;
     int32_t* dir;
     uint32_t *keys, *excl, *hexcl, *hout, *hout_dev;
-    HIP_OK(hipMalloc((void**)&crf, cap * 4));
-    HIP_OK(hipMalloc((void**)&last, cap * 8));
-    HIP_OK(hipMalloc((void**)&fb, cap * 8));
-    HIP_OK(hipMalloc((void**)&dir, cap * 4));
-    HIP_OK(hipMalloc((void**)&keys, cap * 4));
-    HIP_OK(hipMalloc((void**)&excl, cap / 8));
-    HIP_OK(hipHostMalloc((void**)&hexcl, cap / 8, hipHostMallocDefault));
-    HIP_OK(hipHostMalloc((void**)&hout, cap * 4, hipHostMallocMapped));
-    HIP_OK(hipHostGetDevicePointer((void**)&hout_dev, hout, 0));
+    AMDX_HIP(hipMalloc((void**)&crf, cap * 4));
+    AMDX_HIP(hipMalloc((void**)&last, cap * 8));
+    AMDX_HIP(hipMalloc((void**)&fb, cap * 8));
+    AMDX_HIP(hipMalloc((void**)&dir, cap * 4));
+    AMDX_HIP(hipMalloc((void**)&keys, cap * 4));
+    AMDX_HIP(hipMalloc((void**)&excl, cap / 8));
+    AMDX_HIP(hipHostMalloc((void**)&hexcl, cap / 8, hipHostMallocDefault));
+    AMDX_HIP(hipHostMalloc((void**)&hout, cap * 4, hipHostMallocMapped));
+    AMDX_HIP(hipHostGetDevicePointer((void**)&hout_dev, hout, 0));
     std::memset(hexcl, 0, cap / 8);
-    HIP_OK(hipMemsetAsync(dir, 0xFF, cap * 4, internal_stream_));   // -1: no evictable block
-    HIP_OK(hipMemsetAsync(fb, 0, cap * 8, internal_stream_));
+    AMDX_HIP(hipMemsetAsync(dir, 0xFF, cap * 4, internal_stream_));   // -1: no evictable block
+    AMDX_HIP(hipMemsetAsync(fb, 0, cap * 8, internal_stream_));
     if (dev_slots_) {
-      HIP_OK(hipMemcpyAsync(crf, d_crf_, dev_slots_ * 4, hipMemcpyDeviceToDevice, internal_stream_));
-      HIP_OK(hipMemcpyAsync(last, d_last_, dev_slots_ * 8, hipMemcpyDeviceToDevice, internal_stream_));
-      HIP_OK(hipMemcpyAsync(fb, d_fbytes_, dev_slots_ * 8, hipMemcpyDeviceToDevice, internal_stream_));
-      HIP_OK(hipMemcpyAsync(dir, d_dir_, dev_slots_ * 4, hipMemcpyDeviceToDevice, internal_stream_));
+      AMDX_HIP(hipMemcpyAsync(crf, d_crf_, dev_slots_ * 4, hipMemcpyDeviceToDevice, internal_stream_));
+      AMDX_HIP(hipMemcpyAsync(last, d_last_, dev_slots_ * 8, hipMemcpyDeviceToDevice, internal_stream_));
+      AMDX_HIP(hipMemcpyAsync(fb, d_fbytes_, dev_slots_ * 8, hipMemcpyDeviceToDevice, internal_stream_));
+      AMDX_HIP(hipMemcpyAsync(dir, d_dir_, dev_slots_ * 4, hipMemcpyDeviceToDevice, internal_stream_));
     }
-    HIP_OK(hipStreamSynchronize(internal_stream_));
+    AMDX_HIP(hipStreamSynchronize(internal_stream_));
     for (void* p : {(void*)d_crf_, (void*)d_last_, (void*)d_fbytes_, (void*)d_dir_, (void*)d_keys_, (void*)d_excl_})
       if (p) hipFree(p);
     for (void* p : {(void*)h_excl_, (void*)h_out_})
@@ -1544,21 +1537,21 @@ void BlockStore::flush_annotations_locked() {
   const size_t n = dirty_.size();
   const int k = upd_pos_;
   upd_pos_ ^= 1;
-  HIP_OK(hipEventSynchronize(upd_ev_[k]));
+  AMDX_HIP(hipEventSynchronize(upd_ev_[k]));
   if (h_upd_cap_[k] < n) {
     if (h_upd_[k]) hipHostFree(h_upd_[k]);
     h_upd_[k] = nullptr;
     const size_t cap = std::max<size_t>(n, 4096);
-    HIP_OK(hipHostMalloc((void**)&h_upd_[k], cap * sizeof(SlotUpdate), hipHostMallocDefault));
+    AMDX_HIP(hipHostMalloc((void**)&h_upd_[k], cap * sizeof(SlotUpdate), hipHostMallocDefault));
     h_upd_cap_[k] = cap;
   }
   if (d_upd_cap_ < n) {
     // stream-ordered: the previous scatter finished reading the old buffer before this point
-    HIP_OK(hipStreamSynchronize(internal_stream_));
+    AMDX_HIP(hipStreamSynchronize(internal_stream_));
     if (d_upd_) hipFree(d_upd_);
     d_upd_ = nullptr;
     const size_t cap = std::max<size_t>(n, 4096);
-    HIP_OK(hipMalloc((void**)&d_upd_, cap * sizeof(SlotUpdate)));
+    AMDX_HIP(hipMalloc((void**)&d_upd_, cap * sizeof(SlotUpdate)));
     d_upd_cap_ = cap;
   }
   SlotUpdate* u = h_upd_[k];
@@ -1573,9 +1566,9 @@ void BlockStore::flush_annotations_locked() {
     dirty_flag_[s] = 0;
   }
   dirty_.clear();
-  HIP_OK(hipMemcpyAsync(d_upd_, u, n * sizeof(SlotUpdate), hipMemcpyHostToDevice, internal_stream_));
-  HIP_OK(launch_slot_update(dev_state(clock_.load()), d_upd_, (uint32_t)n, internal_stream_));
-  HIP_OK(hipEventRecord(upd_ev_[k], internal_stream_));
+  AMDX_HIP(hipMemcpyAsync(d_upd_, u, n * sizeof(SlotUpdate), hipMemcpyHostToDevice, internal_stream_));
+  AMDX_HIP(launch_slot_update(dev_state(clock_.load()), d_upd_, (uint32_t)n, internal_stream_));
+  AMDX_HIP(hipEventRecord(upd_ev_[k], internal_stream_));
   ++stats_.annotation_flushes;
   stats_.annotation_updates += n;
 }
@@ -2075,8 +2068,8 @@ int64_t BlockStore::mag_device_count(int dir) {
   StorageDir& d = *dirs_.at(dir);
   if (!d.mag_bits) return 0;
   std::vector<uint64_t> w(d.free_bits.size());
-  HIP_OK(hipStreamSynchronize(internal_stream_));
-  HIP_OK(hipMemcpy(w.data(), d.mag_bits, w.size() * 8, hipMemcpyDeviceToHost));
+  AMDX_HIP(hipStreamSynchronize(internal_stream_));
+  AMDX_HIP(hipMemcpy(w.data(), d.mag_bits, w.size() * 8, hipMemcpyDeviceToHost));
   int64_t n = 0;
   for (uint64_t x : w) n += __builtin_popcountll(x);
   return n;
@@ -2092,8 +2085,8 @@ std::string BlockStore::check_pages(int dir) {
   };
   std::vector<uint64_t> mag(d.free_bits.size(), 0);
   if (d.mag_bits) {
-    HIP_OK(hipStreamSynchronize(internal_stream_));
-    HIP_OK(hipMemcpy(mag.data(), d.mag_bits, mag.size() * 8, hipMemcpyDeviceToHost));
+    AMDX_HIP(hipStreamSynchronize(internal_stream_));
+    AMDX_HIP(hipMemcpy(mag.data(), d.mag_bits, mag.size() * 8, hipMemcpyDeviceToHost));
   }
   int64_t host_free = 0, mag_n = 0;
   for (size_t w = 0; w < mag.size(); ++w) {
@@ -2143,16 +2136,16 @@ std::vector<std::vector<int64_t>> BlockStore::mag_claim_many(int dir, const std:
     claim_one_.items_h[i] = ClaimItem{0, 0, wants[i], pb, 0, 0};
     pb += wants[i];
   }
-  HIP_OK(hipMemcpyAsync(claim_one_.items_d, claim_one_.items_h, wants.size() * sizeof(ClaimItem), hipMemcpyHostToDevice,
+  AMDX_HIP(hipMemcpyAsync(claim_one_.items_d, claim_one_.items_h, wants.size() * sizeof(ClaimItem), hipMemcpyHostToDevice,
                         internal_stream_));
   const std::pair<uint32_t, uint32_t> mwin = mag_window(d);
-  HIP_OK(launch_mag_claim_scatter(d.mag_bits, (uint32_t)d.free_bits.size(), claim_one_.items_d, (uint32_t)wants.size(),
+  AMDX_HIP(launch_mag_claim_scatter(d.mag_bits, (uint32_t)d.free_bits.size(), claim_one_.items_d, (uint32_t)wants.size(),
                                   claim_one_.pages_d, (uint32_t)claim_one_.pages_cap, claim_one_.got_d, 0, nullptr, 0,
                                   internal_stream_, mwin.first, mwin.second));
-  HIP_OK(hipMemcpyAsync(claim_one_.got_h, claim_one_.got_d, wants.size() * 4, hipMemcpyDeviceToHost, internal_stream_));
-  HIP_OK(hipMemcpyAsync(claim_one_.pages_h, claim_one_.pages_d, std::max<size_t>(total, 1) * 8, hipMemcpyDeviceToHost,
+  AMDX_HIP(hipMemcpyAsync(claim_one_.got_h, claim_one_.got_d, wants.size() * 4, hipMemcpyDeviceToHost, internal_stream_));
+  AMDX_HIP(hipMemcpyAsync(claim_one_.pages_h, claim_one_.pages_d, std::max<size_t>(total, 1) * 8, hipMemcpyDeviceToHost,
                         internal_stream_));
-  HIP_OK(hipStreamSynchronize(internal_stream_));
+  AMDX_HIP(hipStreamSynchronize(internal_stream_));
   for (size_t i = 0; i < wants.size(); ++i) {
     const ClaimItem& it = claim_one_.items_h[i];
     const uint32_t g = std::min(claim_one_.got_h[i], it.want);
@@ -2407,7 +2400,7 @@ std::vector<int> BlockStore::ingest_files(int64_t session, const std::vector<int
   auto finish = [&](int h) {
     if (pending[h].empty() && claim_[h].ids.empty()) return;
     tick(phase_ns[2]);
-    if (has_device_) HIP_OK(hipStreamSynchronize(st));
+    if (has_device_) AMDX_HIP(hipStreamSynchronize(st));
     tick(phase_ns[3]);
     if (!claim_[h].ids.empty()) {
       const std::unordered_set<int64_t> failed = ingest_device_finish(session, h, lengths, host_half[h], status);
@@ -2549,14 +2542,14 @@ std::vector<int> BlockStore::ingest_files(int64_t session, const std::vector<int
     }
     if (!dev_items.empty()) {
       if (ingest_dev_cap_ < staging_bytes) {
-        HIP_OK(hipStreamSynchronize(st));
+        AMDX_HIP(hipStreamSynchronize(st));
         if (ingest_dev_) hipFree(ingest_dev_);
         ingest_dev_ = nullptr;
-        HIP_OK(hipMalloc(&ingest_dev_, staging_bytes));
+        AMDX_HIP(hipMalloc(&ingest_dev_, staging_bytes));
         ingest_dev_cap_ = staging_bytes;
       }
       uint8_t* dbase = reinterpret_cast<uint8_t*>(ingest_dev_) + h * half;
-      HIP_OK(hipMemcpyAsync(dbase, base, off, hipMemcpyHostToDevice, st));
+      AMDX_HIP(hipMemcpyAsync(dbase, base, off, hipMemcpyHostToDevice, st));
       if (fused_dir >= 0) {
         ingest_device_group(session, ids, lengths, dev_items, at, lo, dbase, h, st, pending[h]);
         claim_[h].dir = fused_dir;
@@ -2605,10 +2598,10 @@ void BlockStore::claim_reserve(ClaimScratch& c, size_t items, size_t pages) {
     c.got_d = nullptr;
     c.got_h = nullptr;
     const size_t cap = std::max<size_t>(items, 1024);
-    HIP_OK(hipMalloc((void**)&c.items_d, cap * sizeof(ClaimItem)));
-    HIP_OK(hipHostMalloc((void**)&c.items_h, cap * sizeof(ClaimItem), hipHostMallocDefault));
-    HIP_OK(hipMalloc((void**)&c.got_d, cap * sizeof(uint32_t)));
-    HIP_OK(hipHostMalloc((void**)&c.got_h, cap * sizeof(uint32_t), hipHostMallocDefault));
+    AMDX_HIP(hipMalloc((void**)&c.items_d, cap * sizeof(ClaimItem)));
+    AMDX_HIP(hipHostMalloc((void**)&c.items_h, cap * sizeof(ClaimItem), hipHostMallocDefault));
+    AMDX_HIP(hipMalloc((void**)&c.got_d, cap * sizeof(uint32_t)));
+    AMDX_HIP(hipHostMalloc((void**)&c.got_h, cap * sizeof(uint32_t), hipHostMallocDefault));
     c.items_cap = cap;
   }
   if (c.pages_cap < pages) {
@@ -2617,8 +2610,8 @@ void BlockStore::claim_reserve(ClaimScratch& c, size_t items, size_t pages) {
     c.pages_d = nullptr;
     c.pages_h = nullptr;
     const size_t cap = std::max<size_t>(pages, 4096);
-    HIP_OK(hipMalloc((void**)&c.pages_d, cap * sizeof(int64_t)));
-    HIP_OK(hipHostMalloc((void**)&c.pages_h, cap * sizeof(int64_t), hipHostMallocDefault));
+    AMDX_HIP(hipMalloc((void**)&c.pages_d, cap * sizeof(int64_t)));
+    AMDX_HIP(hipHostMalloc((void**)&c.pages_h, cap * sizeof(int64_t), hipHostMallocDefault));
     c.pages_cap = cap;
   }
 }
@@ -2665,12 +2658,12 @@ bool BlockStore::ingest_device_group(int64_t session, const std::vector<int64_t>
     c.at.push_back(at[i - lo]);
   }
   const uint32_t nwords = (uint32_t)dirs_[d]->free_bits.size();
-  HIP_OK(hipMemcpyAsync(c.items_d, c.items_h, items.size() * sizeof(ClaimItem), hipMemcpyHostToDevice, st));
-  HIP_OK(launch_mag_claim_scatter(dirs_[d]->mag_bits, nwords, c.items_d, (uint32_t)items.size(), c.pages_d,
+  AMDX_HIP(hipMemcpyAsync(c.items_d, c.items_h, items.size() * sizeof(ClaimItem), hipMemcpyHostToDevice, st));
+  AMDX_HIP(launch_mag_claim_scatter(dirs_[d]->mag_bits, nwords, c.items_d, (uint32_t)items.size(), c.pages_d,
                                   (uint32_t)c.pages_cap, c.got_d, (uint32_t)nchunks,
                                   reinterpret_cast<uint8_t*>(dirs_[d]->spec.base), ps, st, mwin.first, mwin.second));
-  HIP_OK(hipMemcpyAsync(c.pages_h, c.pages_d, npages * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(c.got_h, c.got_d, items.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  AMDX_HIP(hipMemcpyAsync(c.pages_h, c.pages_d, npages * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  AMDX_HIP(hipMemcpyAsync(c.got_h, c.got_d, items.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   for (int64_t id : c.ids) pending.push_back(id);
   return true;
 }

@@ -32,24 +32,9 @@
 #include <vector>
 
 #include "kernels.h"
+#include "store_error.h"
 
 namespace amdx {
-
-struct StoreError : std::runtime_error {
-  int code;
-  StoreError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-// error codes mirrored in Python (alluxio_amd/ops/native.py)
-enum ErrCode {
-  kErrNotFound = 1,
-  kErrAlreadyExists = 2,
-  kErrOutOfSpace = 3,
-  kErrInvalidState = 4,
-  kErrHip = 5,
-  kErrInvalidArgument = 6,
-  kErrIo = 7,
-  kErrTimeout = 8,
-};
 
 enum class DirKind : int { kDevice = 0, kHost = 1, kFile = 2 };
 enum class MemKind : int { kHost = 0, kDevice = 1 };

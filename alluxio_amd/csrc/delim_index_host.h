@@ -2,10 +2,11 @@
 // virtual byte range behind a page table, and its quoted form, which carries the state "inside
 // quotes" along.  No HIP include, so a stand-alone program can compile it.
 #pragma once
-#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <vector>
+
+#include "paged_view_host.h"
 
 namespace amdx {
 
@@ -13,20 +14,14 @@ namespace amdx {
 // `delim`, ascending.  The caller has checked that the range lies inside vtab.
 inline void delim_index_host(const uint8_t* arena, const int64_t* vtab, uint32_t page_shift, uint64_t vstart,
                              uint64_t bytes, uint8_t delim, uint64_t add, std::vector<uint64_t>* out) {
-  const uint64_t psize = 1ull << page_shift, pmask = psize - 1;
-  uint64_t done = 0;
-  while (done < bytes) {
-    const uint64_t va = vstart + done, po = va & pmask;
-    const uint64_t take = std::min(bytes - done, psize - po);
-    const uint8_t* p = arena + ((uint64_t)vtab[va >> page_shift] << page_shift) + po;
-    const uint8_t* e = p + take;
+  for_each_page_run(arena, vtab, page_shift, vstart, bytes, [&](const uint8_t* p, uint64_t n, uint64_t done) {
+    const uint8_t* e = p + n;
     for (const uint8_t* q = p; q < e; ++q) {
       q = static_cast<const uint8_t*>(std::memchr(q, delim, (size_t)(e - q)));
       if (!q) break;
       out->push_back(add + done + (uint64_t)(q - p) + 1);
     }
-    done += take;
-  }
+  });
 }
 
 // The quoted form: a byte equal to `quote` (!= delim) toggles the state "inside quotes", which is
@@ -35,14 +30,9 @@ inline void delim_index_host(const uint8_t* arena, const int64_t* vtab, uint32_t
 inline bool delim_index_host_quoted(const uint8_t* arena, const int64_t* vtab, uint32_t page_shift, uint64_t vstart,
                                     uint64_t bytes, uint8_t delim, uint8_t quote, bool in_quote, uint64_t add,
                                     std::vector<uint64_t>* out) {
-  const uint64_t psize = 1ull << page_shift, pmask = psize - 1;
-  uint64_t done = 0;
   bool inside = in_quote;
-  while (done < bytes) {
-    const uint64_t va = vstart + done, po = va & pmask;
-    const uint64_t take = std::min(bytes - done, psize - po);
-    const uint8_t* p = arena + ((uint64_t)vtab[va >> page_shift] << page_shift) + po;
-    const uint8_t* e = p + take;
+  for_each_page_run(arena, vtab, page_shift, vstart, bytes, [&](const uint8_t* p, uint64_t n, uint64_t done) {
+    const uint8_t* e = p + n;
     const uint8_t* q = p;
     while (q < e) {
       if (inside) {                                 // nothing counts up to the closing quote
@@ -56,8 +46,7 @@ inline bool delim_index_host_quoted(const uint8_t* arena, const int64_t* vtab, u
       if (b == quote) inside = true;
       else if (b == delim) out->push_back(add + done + (uint64_t)(q - p));
     }
-    done += take;
-  }
+  });
   return inside;
 }
 

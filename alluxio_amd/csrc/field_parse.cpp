@@ -5,15 +5,9 @@
 
 #include "block_store.h"
 #include "kernels.h"
+#include "paged_view.h"
 
 namespace amdx {
-
-#define FP_HIP(expr)                                                                           \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess)                                                                      \
-      throw StoreError(kErrHip, std::string("HIP error: ") + hipGetErrorString(_e) + " at " #expr); \
-  } while (0)
 
 namespace {
 
@@ -61,8 +55,8 @@ void field_parse_raw(uint64_t data, uint64_t data_bytes, uint64_t off, uint64_t 
     field_parse_host(a);
     return;
   }
-  FP_HIP(hipSetDevice(device));
-  FP_HIP(launch_field_parse(a, reinterpret_cast<hipStream_t>(stream)));
+  AMDX_HIP(hipSetDevice(device));
+  AMDX_HIP(launch_field_parse(a, reinterpret_cast<hipStream_t>(stream)));
   ++g_launches;
 }
 

@@ -5,16 +5,9 @@
 #include <cstring>
 #include <unordered_map>
 
-#include "block_store.h"   // StoreError, MemKind, error codes
+#include "paged_view.h"   // AMDX_HIP; StoreError, MemKind, error codes (block_store.h)
 
 namespace amdx {
-
-#define PC_HIP_OK(expr)                                                                       \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess)                                                                     \
-      throw StoreError(kErrHip, std::string("HIP error: ") + hipGetErrorString(_e) + " at " + #expr); \
-  } while (0)
 
 static uint64_t next_pow2(uint64_t x) {
   uint64_t p = 64;
@@ -38,23 +31,23 @@ DevicePageCache::DevicePageCache(int device, uint64_t capacity_bytes, uint64_t p
   free_.reserve(nslots_);
   for (uint32_t s = nslots_; s-- > 0;) free_.push_back(s);
   if (use_device_) {
-    PC_HIP_OK(hipSetDevice(device_));
+    AMDX_HIP(hipSetDevice(device_));
     void* p = nullptr;
-    PC_HIP_OK(hipMalloc(&p, nslots_ * page_size_));
+    AMDX_HIP(hipMalloc(&p, nslots_ * page_size_));
     arena_ = (uint64_t)p;
-    PC_HIP_OK(hipMalloc((void**)&table_d_, table_h_.size() * sizeof(PageTableEntry)));
-    PC_HIP_OK(hipMalloc((void**)&stamps_d_, nslots_ * sizeof(uint32_t)));
-    PC_HIP_OK(hipMemset(stamps_d_, 0, nslots_ * sizeof(uint32_t)));
-    PC_HIP_OK(hipMalloc((void**)&slot_key_d_, nslots_ * sizeof(uint64_t)));
-    PC_HIP_OK(hipMalloc((void**)&slot_tidx_d_, nslots_ * sizeof(uint32_t)));
-    PC_HIP_OK(hipMalloc((void**)&free_stack_d_, nslots_ * sizeof(uint32_t)));
-    PC_HIP_OK(hipMalloc((void**)&hist_d_, kPutAgeBuckets * sizeof(uint32_t)));
-    PC_HIP_OK(hipMalloc((void**)&table2_d_, table_h_.size() * sizeof(PageTableEntry)));
-    PC_HIP_OK(hipMalloc((void**)&tag_d_, table_h_.size() * sizeof(unsigned long long)));
-    PC_HIP_OK(hipMemset(tag_d_, 0, table_h_.size() * sizeof(unsigned long long)));
-    PC_HIP_OK(hipMalloc((void**)&ctr_d_, sizeof(PutCounters)));
-    PC_HIP_OK(hipMemset(ctr_d_, 0, sizeof(PutCounters)));
-    PC_HIP_OK(hipHostMalloc((void**)&ctr_h_, sizeof(PutCounters), hipHostMallocDefault));
+    AMDX_HIP(hipMalloc((void**)&table_d_, table_h_.size() * sizeof(PageTableEntry)));
+    AMDX_HIP(hipMalloc((void**)&stamps_d_, nslots_ * sizeof(uint32_t)));
+    AMDX_HIP(hipMemset(stamps_d_, 0, nslots_ * sizeof(uint32_t)));
+    AMDX_HIP(hipMalloc((void**)&slot_key_d_, nslots_ * sizeof(uint64_t)));
+    AMDX_HIP(hipMalloc((void**)&slot_tidx_d_, nslots_ * sizeof(uint32_t)));
+    AMDX_HIP(hipMalloc((void**)&free_stack_d_, nslots_ * sizeof(uint32_t)));
+    AMDX_HIP(hipMalloc((void**)&hist_d_, kPutAgeBuckets * sizeof(uint32_t)));
+    AMDX_HIP(hipMalloc((void**)&table2_d_, table_h_.size() * sizeof(PageTableEntry)));
+    AMDX_HIP(hipMalloc((void**)&tag_d_, table_h_.size() * sizeof(unsigned long long)));
+    AMDX_HIP(hipMemset(tag_d_, 0, table_h_.size() * sizeof(unsigned long long)));
+    AMDX_HIP(hipMalloc((void**)&ctr_d_, sizeof(PutCounters)));
+    AMDX_HIP(hipMemset(ctr_d_, 0, sizeof(PutCounters)));
+    AMDX_HIP(hipHostMalloc((void**)&ctr_h_, sizeof(PutCounters), hipHostMallocDefault));
     ring_.init();
   } else {
     void* p = std::aligned_alloc(64, ((nslots_ * page_size_ + 63) / 64) * 64);
@@ -168,9 +161,9 @@ void DevicePageCache::flush_table(hipStream_t stream) {
   // a gather queued on another stream may still be probing the entries about to change
   order_after_readers(stream);
   if (full_upload_) {
-    PC_HIP_OK(hipMemcpyAsync(table_d_, table_h_.data(), table_h_.size() * sizeof(PageTableEntry),
+    AMDX_HIP(hipMemcpyAsync(table_d_, table_h_.data(), table_h_.size() * sizeof(PageTableEntry),
                              hipMemcpyHostToDevice, stream));
-    PC_HIP_OK(hipStreamSynchronize(stream));   // the host mirror may change right after
+    AMDX_HIP(hipStreamSynchronize(stream));   // the host mirror may change right after
     full_upload_ = false;
     for (uint64_t i : dirty_) dirty_flag_[i] = 0;
     dirty_.clear();
@@ -182,18 +175,18 @@ void DevicePageCache::flush_table(hipStream_t stream) {
     hipFree(upd_idx_d_);
     hipFree(upd_ent_d_);
     upd_cap_ = std::max<uint32_t>(n, 1024);
-    PC_HIP_OK(hipMalloc((void**)&upd_idx_d_, upd_cap_ * sizeof(uint64_t)));
-    PC_HIP_OK(hipMalloc((void**)&upd_ent_d_, upd_cap_ * sizeof(PageTableEntry)));
+    AMDX_HIP(hipMalloc((void**)&upd_idx_d_, upd_cap_ * sizeof(uint64_t)));
+    AMDX_HIP(hipMalloc((void**)&upd_ent_d_, upd_cap_ * sizeof(PageTableEntry)));
   }
   std::vector<PageTableEntry> ents(n);
   for (uint32_t i = 0; i < n; ++i) {
     ents[i] = table_h_[dirty_[i]];
     dirty_flag_[dirty_[i]] = 0;
   }
-  PC_HIP_OK(hipMemcpyAsync(upd_idx_d_, dirty_.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-  PC_HIP_OK(hipMemcpyAsync(upd_ent_d_, ents.data(), n * sizeof(PageTableEntry), hipMemcpyHostToDevice, stream));
-  PC_HIP_OK(launch_page_table_update(table_d_, upd_idx_d_, upd_ent_d_, n, stream));
-  PC_HIP_OK(hipStreamSynchronize(stream));     // pageable sources: keep them alive until copied
+  AMDX_HIP(hipMemcpyAsync(upd_idx_d_, dirty_.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+  AMDX_HIP(hipMemcpyAsync(upd_ent_d_, ents.data(), n * sizeof(PageTableEntry), hipMemcpyHostToDevice, stream));
+  AMDX_HIP(launch_page_table_update(table_d_, upd_idx_d_, upd_ent_d_, n, stream));
+  AMDX_HIP(hipStreamSynchronize(stream));     // pageable sources: keep them alive until copied
   dirty_.clear();
 }
 
@@ -202,7 +195,7 @@ void DevicePageCache::sync_device_stamps() {
   if (!use_device_ || !device_stamps_dirty_) return;
   std::vector<uint32_t> dev(nslots_);
   wait_gathers();
-  PC_HIP_OK(hipMemcpy(dev.data(), stamps_d_, nslots_ * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  AMDX_HIP(hipMemcpy(dev.data(), stamps_d_, nslots_ * sizeof(uint32_t), hipMemcpyDeviceToHost));
   for (uint32_t s = 0; s < nslots_; ++s) stamp_h_[s] = std::max(stamp_h_[s], dev[s]);
   device_stamps_dirty_ = false;
 }
@@ -238,7 +231,7 @@ void DevicePageCache::wait_gathers() {
     ev_pool_.push_back(ev);
   }
   pending_ev_.clear();
-  PC_HIP_OK(first);
+  AMDX_HIP(first);
 }
 
 void DevicePageCache::track_reader(hipStream_t stream) {
@@ -254,18 +247,18 @@ void DevicePageCache::track_reader(hipStream_t stream) {
     ev = ev_pool_.back();
     ev_pool_.pop_back();
   } else {
-    PC_HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    AMDX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   }
   const hipError_t e = hipEventRecord(ev, stream);
   if (e != hipSuccess) {
     ev_pool_.push_back(ev);
-    PC_HIP_OK(e);
+    AMDX_HIP(e);
   }
   pending_ev_.push_back(ev);
 }
 
 void DevicePageCache::order_after_readers(hipStream_t stream) {
-  for (hipEvent_t ev : pending_ev_) PC_HIP_OK(hipStreamWaitEvent(stream, ev, 0));
+  for (hipEvent_t ev : pending_ev_) AMDX_HIP(hipStreamWaitEvent(stream, ev, 0));
 }
 
 // ---- public API -------------------------------------------------------------------------------
@@ -295,8 +288,8 @@ std::vector<uint64_t> DevicePageCache::put(uint64_t key, uint64_t src, uint64_t 
   if (len) {
     if (use_device_) {
       const hipMemcpyKind kind = src_kind == (int)MemKind::kDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-      PC_HIP_OK(hipMemcpyAsync((void*)dst, (const void*)src, len, kind, (hipStream_t)stream));
-      PC_HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+      AMDX_HIP(hipMemcpyAsync((void*)dst, (const void*)src, len, kind, (hipStream_t)stream));
+      AMDX_HIP(hipStreamSynchronize((hipStream_t)stream));
     } else {
       std::memcpy((void*)dst, (const void*)src, len);
     }
@@ -344,13 +337,13 @@ std::vector<uint64_t> DevicePageCache::put_many(const std::vector<uint64_t>& key
       lens_d_ = nullptr;
       keys_cap_ = 0;
       const uint32_t cap = std::max<uint32_t>(n, 4096);
-      PC_HIP_OK(hipMalloc((void**)&keys_d_, cap * sizeof(uint64_t)));
-      PC_HIP_OK(hipMalloc((void**)&slots_d_, cap * sizeof(int32_t)));
-      PC_HIP_OK(hipMalloc((void**)&lens_d_, cap * sizeof(uint32_t)));
+      AMDX_HIP(hipMalloc((void**)&keys_d_, cap * sizeof(uint64_t)));
+      AMDX_HIP(hipMalloc((void**)&slots_d_, cap * sizeof(int32_t)));
+      AMDX_HIP(hipMalloc((void**)&lens_d_, cap * sizeof(uint32_t)));
       keys_cap_ = cap;
     }
     order_after_readers(s);
-    PC_HIP_OK(hipMemcpyAsync(keys_d_, keys_in.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    AMDX_HIP(hipMemcpyAsync(keys_d_, keys_in.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     return put_device_locked(keys_d_, n, src, src_stride, len, src_kind, s, evict);
   }
   ensure_host();
@@ -387,12 +380,12 @@ std::vector<uint64_t> DevicePageCache::put_many(const std::vector<uint64_t>& key
         if (!use_device_) {
           for (const auto& sg : segs) std::memcpy((void*)sg.dst, (const void*)sg.src, sg.bytes);
         } else if (src_kind == (int)MemKind::kDevice) {
-          PC_HIP_OK(ring_.launch(segs, st));
-          PC_HIP_OK(hipStreamSynchronize(st));
+          AMDX_HIP(ring_.launch(segs, st));
+          AMDX_HIP(hipStreamSynchronize(st));
         } else {
           for (const auto& sg : segs)
-            PC_HIP_OK(hipMemcpyAsync((void*)sg.dst, (const void*)sg.src, sg.bytes, hipMemcpyHostToDevice, st));
-          PC_HIP_OK(hipStreamSynchronize(st));
+            AMDX_HIP(hipMemcpyAsync((void*)sg.dst, (const void*)sg.src, sg.bytes, hipMemcpyHostToDevice, st));
+          AMDX_HIP(hipStreamSynchronize(st));
         }
       } catch (...) {
         rollback();
@@ -474,8 +467,8 @@ bool DevicePageCache::read(uint64_t key, uint64_t offset, uint64_t len, uint64_t
   if (len == 0) return true;
   if (use_device_) {
     const hipMemcpyKind kind = dst_kind == (int)MemKind::kDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    PC_HIP_OK(hipMemcpyAsync((void*)dst, (const void*)src, len, kind, (hipStream_t)stream));
-    PC_HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+    AMDX_HIP(hipMemcpyAsync((void*)dst, (const void*)src, len, kind, (hipStream_t)stream));
+    AMDX_HIP(hipStreamSynchronize((hipStream_t)stream));
   } else {
     std::memcpy((void*)dst, (const void*)src, len);
   }
@@ -513,12 +506,12 @@ std::vector<int32_t> DevicePageCache::read_segments(const std::vector<uint64_t>&
     return missed;
   }
   if (dst_kind == (int)MemKind::kDevice) {
-    PC_HIP_OK(ring_.launch(segs, st));
+    AMDX_HIP(ring_.launch(segs, st));
     track_reader(st);
   } else {
     for (const auto& sg : segs)
-      PC_HIP_OK(hipMemcpyAsync((void*)sg.dst, (const void*)sg.src, sg.bytes, hipMemcpyDeviceToHost, st));
-    PC_HIP_OK(hipStreamSynchronize(st));
+      AMDX_HIP(hipMemcpyAsync((void*)sg.dst, (const void*)sg.src, sg.bytes, hipMemcpyDeviceToHost, st));
+    AMDX_HIP(hipStreamSynchronize(st));
   }
   return missed;
 }
@@ -556,7 +549,7 @@ void DevicePageCache::gather_locked(uint64_t keys, uint32_t n, uint64_t dst, uin
   flush_table(s);
   PageGatherArgs a{table_d_, table_h_.size() - 1, (const uint64_t*)keys, n, (const uint8_t*)arena_, page_size_,
                    (uint8_t*)dst, dst_stride, (int32_t*)slot_out, (uint32_t*)len_out, stamps_d_, epoch};
-  PC_HIP_OK(launch_page_lookup_gather(a, s));
+  AMDX_HIP(launch_page_lookup_gather(a, s));
   track_reader(s);
   device_stamps_dirty_ = true;
 }
@@ -585,17 +578,17 @@ std::vector<int32_t> DevicePageCache::gather_host_keys(const std::vector<uint64_
     lens_d_ = nullptr;
     keys_cap_ = 0;
     const uint32_t cap = std::max<uint32_t>(n, 4096);
-    PC_HIP_OK(hipMalloc((void**)&keys_d_, cap * sizeof(uint64_t)));
-    PC_HIP_OK(hipMalloc((void**)&slots_d_, cap * sizeof(int32_t)));
-    PC_HIP_OK(hipMalloc((void**)&lens_d_, cap * sizeof(uint32_t)));
+    AMDX_HIP(hipMalloc((void**)&keys_d_, cap * sizeof(uint64_t)));
+    AMDX_HIP(hipMalloc((void**)&slots_d_, cap * sizeof(int32_t)));
+    AMDX_HIP(hipMalloc((void**)&lens_d_, cap * sizeof(uint32_t)));
     keys_cap_ = cap;
   }
   // an earlier call's gather (another stream) may still read keys_d_
   order_after_readers(s);
-  PC_HIP_OK(hipMemcpyAsync(keys_d_, keys.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+  AMDX_HIP(hipMemcpyAsync(keys_d_, keys.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
   gather_locked((uint64_t)keys_d_, n, dst, dst_stride, (uint64_t)slots_d_, (uint64_t)lens_d_, s);
-  PC_HIP_OK(hipMemcpyAsync(slots.data(), slots_d_, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  PC_HIP_OK(hipStreamSynchronize(s));
+  AMDX_HIP(hipMemcpyAsync(slots.data(), slots_d_, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  AMDX_HIP(hipStreamSynchronize(s));
   return slots;
 }
 
@@ -611,9 +604,9 @@ void DevicePageCache::reserve_put(uint32_t n) {
   put_ev_d_ = nullptr;
   put_cap_ = 0;
   const uint32_t cap = std::max<uint32_t>(n, 4096);
-  PC_HIP_OK(hipMalloc((void**)&put_tidx_d_, cap * sizeof(uint32_t)));
-  PC_HIP_OK(hipMalloc((void**)&put_slot_d_, cap * sizeof(int32_t)));
-  PC_HIP_OK(hipMalloc((void**)&put_ev_d_, cap * sizeof(uint64_t)));
+  AMDX_HIP(hipMalloc((void**)&put_tidx_d_, cap * sizeof(uint32_t)));
+  AMDX_HIP(hipMalloc((void**)&put_slot_d_, cap * sizeof(int32_t)));
+  AMDX_HIP(hipMalloc((void**)&put_ev_d_, cap * sizeof(uint64_t)));
   put_cap_ = cap;
 }
 
@@ -626,27 +619,27 @@ void DevicePageCache::ensure_device(hipStream_t stream) {
     const auto& e = table_h_[i];
     if (e.key != kPageKeyEmpty && e.key != kPageKeyTomb && e.slot >= 0) tidx[e.slot] = (uint32_t)i;
   }
-  PC_HIP_OK(hipMemcpyAsync(slot_key_d_, slot_key_.data(), nslots_ * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-  PC_HIP_OK(hipMemcpyAsync(slot_tidx_d_, tidx.data(), nslots_ * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  AMDX_HIP(hipMemcpyAsync(slot_key_d_, slot_key_.data(), nslots_ * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+  AMDX_HIP(hipMemcpyAsync(slot_tidx_d_, tidx.data(), nslots_ * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
   if (!free_.empty())
-    PC_HIP_OK(hipMemcpyAsync(free_stack_d_, free_.data(), free_.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+    AMDX_HIP(hipMemcpyAsync(free_stack_d_, free_.data(), free_.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
                              stream));
-  PC_HIP_OK(hipMemcpyAsync(stamps_d_, stamp_h_.data(), nslots_ * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  AMDX_HIP(hipMemcpyAsync(stamps_d_, stamp_h_.data(), nslots_ * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
   ctr_h_->free_top = (int32_t)free_.size();
-  PC_HIP_OK(hipMemcpyAsync(&ctr_d_->free_top, &ctr_h_->free_top, sizeof(int32_t), hipMemcpyHostToDevice, stream));
-  PC_HIP_OK(hipStreamSynchronize(stream));       // pageable sources
+  AMDX_HIP(hipMemcpyAsync(&ctr_d_->free_top, &ctr_h_->free_top, sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  AMDX_HIP(hipStreamSynchronize(stream));       // pageable sources
   host_changed_ = false;
 }
 
 void DevicePageCache::ensure_host() {
   if (!dev_owner_) return;
   wait_gathers();                                // device puts already completed on their stream
-  PC_HIP_OK(hipMemcpy(table_h_.data(), table_d_, table_h_.size() * sizeof(PageTableEntry), hipMemcpyDeviceToHost));
-  PC_HIP_OK(hipMemcpy(slot_key_.data(), slot_key_d_, nslots_ * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  PC_HIP_OK(hipMemcpy(ctr_h_, ctr_d_, sizeof(PutCounters), hipMemcpyDeviceToHost));
+  AMDX_HIP(hipMemcpy(table_h_.data(), table_d_, table_h_.size() * sizeof(PageTableEntry), hipMemcpyDeviceToHost));
+  AMDX_HIP(hipMemcpy(slot_key_.data(), slot_key_d_, nslots_ * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  AMDX_HIP(hipMemcpy(ctr_h_, ctr_d_, sizeof(PutCounters), hipMemcpyDeviceToHost));
   const int32_t top = std::max<int32_t>(0, ctr_h_->free_top);
   free_.assign(top, 0);
-  if (top) PC_HIP_OK(hipMemcpy(free_.data(), free_stack_d_, top * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (top) AMDX_HIP(hipMemcpy(free_.data(), free_stack_d_, top * sizeof(uint32_t), hipMemcpyDeviceToHost));
   tombstones_ = 0;
   for (const auto& e : table_h_) tombstones_ += e.key == kPageKeyTomb;
   for (uint64_t i : dirty_) dirty_flag_[i] = 0;
@@ -703,39 +696,39 @@ std::vector<uint64_t> DevicePageCache::put_device_locked(const uint64_t* keys_d,
   a.arena = (uint8_t*)arena_;
   a.page_size = page_size_;
   // nfresh .. nfail start at 0 (free_top and the CLOCK hand carry over)
-  PC_HIP_OK(hipMemsetAsync(&ctr_d_->nfresh, 0, 4 * sizeof(uint32_t), s));
-  PC_HIP_OK(launch_page_put_probe(a, s));
+  AMDX_HIP(hipMemsetAsync(&ctr_d_->nfresh, 0, 4 * sizeof(uint32_t), s));
+  AMDX_HIP(launch_page_put_probe(a, s));
   dev_owner_ = true;                             // the device table changed from here on
   if (!evict) {
-    PC_HIP_OK(hipMemcpyAsync(c, ctr_d_, sizeof(PutCounters), hipMemcpyDeviceToHost, s));
-    PC_HIP_OK(hipStreamSynchronize(s));
+    AMDX_HIP(hipMemcpyAsync(c, ctr_d_, sizeof(PutCounters), hipMemcpyDeviceToHost, s));
+    AMDX_HIP(hipStreamSynchronize(s));
     if (c->nfail || (int64_t)c->nfresh > (int64_t)std::max<int32_t>(0, c->free_top)) {
-      PC_HIP_OK(launch_page_put_revert(a, s));
-      PC_HIP_OK(hipMemcpyAsync(c, ctr_d_, sizeof(PutCounters), hipMemcpyDeviceToHost, s));
-      PC_HIP_OK(hipStreamSynchronize(s));
+      AMDX_HIP(launch_page_put_revert(a, s));
+      AMDX_HIP(hipMemcpyAsync(c, ctr_d_, sizeof(PutCounters), hipMemcpyDeviceToHost, s));
+      AMDX_HIP(hipStreamSynchronize(s));
       dev_free_ = std::max<int32_t>(0, c->free_top);
       tombstones_ += c->ntomb;
       throw StoreError(kErrOutOfSpace, "page cache is full");
     }
   }
-  if (evict) PC_HIP_OK(launch_page_put_threshold(a, s));
-  PC_HIP_OK(launch_page_put_assign(a, s));
-  PC_HIP_OK(launch_page_put_fill(a, s));
+  if (evict) AMDX_HIP(launch_page_put_threshold(a, s));
+  AMDX_HIP(launch_page_put_assign(a, s));
+  AMDX_HIP(launch_page_put_fill(a, s));
   // tombstones piling up: rebuild the table on the device, in the same stream order
   const bool rebuild = tombstones_ + n > table_h_.size() / 8;
   if (rebuild) {
-    PC_HIP_OK(launch_page_table_rebuild(a, table2_d_, s));
+    AMDX_HIP(launch_page_table_rebuild(a, table2_d_, s));
     std::swap(table_d_, table2_d_);
   }
-  PC_HIP_OK(hipMemcpyAsync(c, ctr_d_, sizeof(PutCounters), hipMemcpyDeviceToHost, s));
-  PC_HIP_OK(hipStreamSynchronize(s));
+  AMDX_HIP(hipMemcpyAsync(c, ctr_d_, sizeof(PutCounters), hipMemcpyDeviceToHost, s));
+  AMDX_HIP(hipStreamSynchronize(s));
   std::vector<uint64_t> evicted(std::min<uint32_t>(c->nevicted, n));
   if (!evicted.empty())
-    PC_HIP_OK(hipMemcpy(evicted.data(), put_ev_d_, evicted.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    AMDX_HIP(hipMemcpy(evicted.data(), put_ev_d_, evicted.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
   if (c->free_top < 0) {
     c->free_top = 0;
-    PC_HIP_OK(hipMemcpyAsync(&ctr_d_->free_top, &c->free_top, sizeof(int32_t), hipMemcpyHostToDevice, s));
-    PC_HIP_OK(hipStreamSynchronize(s));
+    AMDX_HIP(hipMemcpyAsync(&ctr_d_->free_top, &c->free_top, sizeof(int32_t), hipMemcpyHostToDevice, s));
+    AMDX_HIP(hipStreamSynchronize(s));
   }
   dev_free_ = c->free_top;
   tombstones_ = rebuild ? 0 : tombstones_ + c->ntomb;

@@ -8,13 +8,6 @@
 
 namespace amdx {
 
-#define RG_HIP(expr)                                                                           \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess)                                                                      \
-      throw StoreError(kErrHip, std::string("HIP error: ") + hipGetErrorString(_e) + " at " #expr); \
-  } while (0)
-
 static bool g_index_copy = false;
 void RaggedGatherSession::set_index_copy(bool on) { g_index_copy = on; }
 
@@ -22,104 +15,70 @@ static void bad(const std::string& what) { throw StoreError(kErrInvalidArgument,
 
 RaggedGatherSession::RaggedGatherSession(BlockStore* store, int64_t session, const std::vector<FileBlocks>& files,
                                          const std::vector<std::vector<uint64_t>>& offsets)
-    : store_(store), session_(session) {
+    : store_(store), session_(session), pins_(store) {
   if (files.empty() || files.size() != offsets.size()) bad("one offset array per file is required");
-  try {
-    for (size_t f = 0; f < files.size(); ++f) {
-      const std::vector<int64_t>& ids = files[f].first;
-      const std::vector<uint64_t>& lens = files[f].second;
-      if (ids.size() != lens.size()) bad("bad block list");
-      const uint64_t vpage0 = vtab_.size();   // every file starts on a fresh virtual page
-      uint64_t file_len = 0;
-      for (size_t b = 0; b < ids.size(); ++b) {
-        locks_.push_back(store_->lock_block(session_, ids[b], false, -1));
-        int dir = -1;
-        uint64_t ps = 0, base = 0;
-        std::vector<int64_t> pages = store_->block_pages(ids[b], &dir, &ps, &base);
-        const DirSpec spec = store_->dir_spec(dir);
-        if (spec.kind == DirKind::kFile) bad("block in a file tier");
-        if (dir_ < 0) {
-          dir_ = dir;
-          page_size_ = ps;
-          arena_ = base;
-          arena_device_ = spec.kind == DirKind::kDevice;
-          if (ps < 16 || (ps & (ps - 1))) bad("page size must be a power of two");
-          while ((1ull << page_shift_) < ps) ++page_shift_;
-        } else if (dir != dir_) {
-          bad("blocks span several dirs");
-        }
-        const uint64_t np = (lens[b] + ps - 1) / ps;
-        if (b + 1 < ids.size() && lens[b] % ps != 0) bad("block size must be a multiple of the page size");
-        if (pages.size() < np) throw StoreError(kErrInvalidState, "ragged gather: block shorter than its length");
-        vtab_.insert(vtab_.end(), pages.begin(), pages.begin() + np);
-        file_len += lens[b];
-      }
-      const std::vector<uint64_t>& off = offsets[f];
-      if (off.empty()) bad("an offset array needs at least one entry");
-      if (off.back() > file_len) bad("record offsets run past the end of the file");
-      if (off.size() > 1 && dir_ < 0) bad("records in a file without blocks");
-      const uint64_t vbase = vpage0 << page_shift_;
-      for (size_t i = 0; i + 1 < off.size(); ++i) {
-        if (off[i + 1] < off[i]) bad("record offsets must not decrease");
-        if (off[i + 1] - off[i] > 0xFFFFFFFFull - 256) bad("record longer than 4 GiB");
-        rec_start_.push_back(vbase + off[i]);
-        rec_len_.push_back((uint32_t)(off[i + 1] - off[i]));
-      }
+  for (size_t f = 0; f < files.size(); ++f) {
+    const auto [vpage0, file_len] =
+        view_.append_file(store_, pins_, session_, files[f].first, files[f].second, "ragged gather");
+    const std::vector<uint64_t>& off = offsets[f];
+    if (off.empty()) bad("an offset array needs at least one entry");
+    if (off.back() > file_len) bad("record offsets run past the end of the file");
+    if (off.size() > 1 && view_.dir < 0) bad("records in a file without blocks");
+    const uint64_t vbase = vpage0 << view_.page_shift;
+    for (size_t i = 0; i + 1 < off.size(); ++i) {
+      if (off[i + 1] < off[i]) bad("record offsets must not decrease");
+      if (off[i + 1] - off[i] > 0xFFFFFFFFull - 256) bad("record longer than 4 GiB");
+      rec_start_.push_back(vbase + off[i]);
+      rec_len_.push_back((uint32_t)(off[i + 1] - off[i]));
     }
-    on_device_ = arena_device_;
-    if (on_device_ && !store_->has_device()) throw StoreError(kErrInvalidState, "ragged gather: device dir without a device");
-    finish_init();
-  } catch (...) {
-    close();
-    throw;
   }
+  on_device_ = view_.arena_device;
+  if (on_device_ && !store_->has_device()) throw StoreError(kErrInvalidState, "ragged gather: device dir without a device");
+  finish_init();
 }
 
 RaggedGatherSession::RaggedGatherSession(uint64_t arena_base, const std::vector<int64_t>& pages, uint64_t page_size,
                                          int device, const std::vector<uint64_t>& rec_start,
                                          const std::vector<uint32_t>& rec_len)
-    : store_(nullptr), device_(device), on_device_(device >= 0), arena_device_(device >= 0), page_size_(page_size),
-      arena_(arena_base), vtab_(pages), rec_start_(rec_start), rec_len_(rec_len) {
-  if (page_size_ < 16 || (page_size_ & (page_size_ - 1))) bad("page size must be a power of two");
-  while ((1ull << page_shift_) < page_size_) ++page_shift_;
+    : store_(nullptr), pins_(nullptr), device_(device), on_device_(device >= 0), rec_start_(rec_start),
+      rec_len_(rec_len) {
+  view_ = PagedView::raw(arena_base, pages, page_size, device, "ragged gather");
   if (rec_start_.size() != rec_len_.size()) bad("record starts and lengths differ in number");
-  const uint64_t vbytes = (uint64_t)vtab_.size() << page_shift_;
-  for (int64_t p : vtab_)
-    if (p < 0) bad("negative arena page");
+  const uint64_t vbytes = view_.bytes();
   for (size_t i = 0; i < rec_len_.size(); ++i) {
     if (rec_len_[i] > 0xFFFFFFFFull - 256) bad("record longer than 4 GiB");
     if (rec_start_[i] > vbytes || rec_len_[i] > vbytes - rec_start_[i]) bad("record outside the page table");
   }
-  try {
-    finish_init();
-  } catch (...) {
-    close();
-    throw;
-  }
+  finish_init();
 }
 
 void RaggedGatherSession::set_device() const {
   if (store_) store_->use_device();
-  else if (device_ >= 0) RG_HIP(hipSetDevice(device_));
+  else if (device_ >= 0) AMDX_HIP(hipSetDevice(device_));
 }
 
 void RaggedGatherSession::finish_init() {
   if (!on_device_) return;
-  if (arena_ & 15) bad("arena base must be 16-byte aligned");
+  if (view_.arena & 15) bad("arena base must be 16-byte aligned");
   set_device();
-  const size_t nv = std::max<size_t>(vtab_.size(), 1), nr = std::max<size_t>(rec_len_.size(), 1);
-  RG_HIP(hipMalloc((void**)&d_vtab_, nv * sizeof(int64_t)));
-  RG_HIP(hipMalloc(&d_recs_, nr * sizeof(RaggedRec)));
-  RG_HIP(hipMalloc((void**)&d_idx_, (size_t)kRaggedGatherMaxBatch * sizeof(int64_t)));
-  RG_HIP(hipMalloc(&d_rows_, (size_t)kRaggedGatherMaxBatch * sizeof(RaggedRow)));
-  RG_HIP(hipMalloc((void**)&d_chunk_pre_, ((size_t)kRaggedGatherMaxBatch + 1) * sizeof(uint32_t)));
-  if (!vtab_.empty()) RG_HIP(hipMemcpy(d_vtab_, vtab_.data(), vtab_.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+  const std::vector<int64_t>& vtab = view_.vtab;
+  d_vtab_.alloc(vtab.size() * sizeof(int64_t));
+  d_recs_.alloc(rec_len_.size() * sizeof(RaggedRec));
+  d_idx_.alloc((size_t)kRaggedGatherMaxBatch * sizeof(int64_t));
+  d_rows_.alloc((size_t)kRaggedGatherMaxBatch * sizeof(RaggedRow));
+  d_chunk_pre_.alloc(((size_t)kRaggedGatherMaxBatch + 1) * sizeof(uint32_t));
+  if (!vtab.empty()) AMDX_HIP(hipMemcpy(d_vtab_.p, vtab.data(), vtab.size() * sizeof(int64_t), hipMemcpyHostToDevice));
   if (!rec_len_.empty()) {
     std::vector<RaggedRec> recs(rec_len_.size());
     for (size_t i = 0; i < recs.size(); ++i) recs[i] = RaggedRec{rec_start_[i], rec_len_[i], 0};
-    RG_HIP(hipMemcpy(d_recs_, recs.data(), recs.size() * sizeof(RaggedRec), hipMemcpyHostToDevice));
+    AMDX_HIP(hipMemcpy(d_recs_.p, recs.data(), recs.size() * sizeof(RaggedRec), hipMemcpyHostToDevice));
   }
-  for (int s = 0; s < kSlots; ++s) RG_HIP(hipEventCreateWithFlags(&ev_[s], hipEventDisableTiming));
+  try {
+    for (int s = 0; s < kSlots; ++s) AMDX_HIP(hipEventCreateWithFlags(&ev_[s], hipEventDisableTiming));
+  } catch (...) {
+    close();   // the events are no members with destructors
+    throw;
+  }
 }
 
 RaggedGatherSession::~RaggedGatherSession() {
@@ -132,23 +91,14 @@ RaggedGatherSession::~RaggedGatherSession() {
 void RaggedGatherSession::close() {
   if (closed_) return;
   closed_ = true;
-  if (on_device_ && d_vtab_) {
+  if (on_device_ && d_vtab_.p) {
     try {
       set_device();
     } catch (...) {
     }
     if (gathers_) (void)hipStreamSynchronize(reinterpret_cast<hipStream_t>(last_stream_));
   }
-  if (d_vtab_) (void)hipFree(d_vtab_);
-  if (d_recs_) (void)hipFree(d_recs_);
-  if (d_idx_) (void)hipFree(d_idx_);
-  if (d_rows_) (void)hipFree(d_rows_);
-  if (d_chunk_pre_) (void)hipFree(d_chunk_pre_);
-  d_vtab_ = nullptr;
-  d_recs_ = nullptr;
-  d_idx_ = nullptr;
-  d_rows_ = nullptr;
-  d_chunk_pre_ = nullptr;
+  for (DevBuf* b : {&d_vtab_, &d_recs_, &d_idx_, &d_rows_, &d_chunk_pre_}) b->reset();
   for (int s = 0; s < kSlots; ++s) {
     if (h_idx_[s]) (void)hipHostFree(h_idx_[s]);
     if (ev_[s]) (void)hipEventDestroy(ev_[s]);
@@ -156,13 +106,7 @@ void RaggedGatherSession::close() {
     h_cap_[s] = 0;
     ev_[s] = nullptr;
   }
-  for (int64_t l : locks_) {
-    try {
-      if (store_) store_->unlock(l);
-    } catch (...) {
-    }
-  }
-  locks_.clear();
+  pins_.release();
 }
 
 uint64_t RaggedGatherSession::gather(const int64_t* idx, uint64_t batch, uint64_t dst, uint64_t capacity,
@@ -178,7 +122,7 @@ uint64_t RaggedGatherSession::gather(const int64_t* idx, uint64_t batch, uint64_
   }
   const bool to_device = dst_kind == (int)MemKind::kDevice;
   if (to_device && !on_device_) bad("device destination but the arena is host memory");
-  if (!to_device && arena_device_) bad("host destination but the arena is device memory");
+  if (!to_device && view_.arena_device) bad("host destination but the arena is device memory");
   // One pass over the record numbers: range check, total size, work items of the copy launch.
   const uint64_t n = rec_len_.size();
   const uint32_t chunk_shift = ragged_gather_chunk_shift();
@@ -211,7 +155,6 @@ uint64_t RaggedGatherSession::gather(const int64_t* idx, uint64_t batch, uint64_
   if (!to_device) {
     uint64_t* off = reinterpret_cast<uint64_t*>(out_off);
     uint32_t* ol = reinterpret_cast<uint32_t*>(out_len);
-    const uint64_t pmask = page_size_ - 1;
     uint64_t o = 0;
     for (uint64_t r = 0; r < batch; ++r) {
       const size_t id = (size_t)idx[r];
@@ -224,16 +167,8 @@ uint64_t RaggedGatherSession::gather(const int64_t* idx, uint64_t batch, uint64_
         adv = span = (len + lay.align - 1) & ~(uint64_t)(lay.align - 1);
       }
       uint8_t* d = reinterpret_cast<uint8_t*>(dst + o);
-      uint64_t done = 0;
-      while (done < len) {
-        const uint64_t va = rec_start_[id] + done;
-        const uint64_t po = va & pmask;
-        const uint64_t take = std::min(len - done, page_size_ - po);
-        std::memcpy(d + done,
-                    reinterpret_cast<const uint8_t*>(arena_ + ((uint64_t)vtab_[va >> page_shift_] << page_shift_) + po),
-                    take);
-        done += take;
-      }
+      for_each_page_run(view_.base(), view_.vtab.data(), view_.page_shift, rec_start_[id], len,
+                        [d](const uint8_t* p, uint64_t n, uint64_t done) { std::memcpy(d + done, p, n); });
       if (span > len) std::memset(d + len, lay.padded ? (int)lay.pad_value : 0, span - len);
       off[r] = o;
       ol[r] = (uint32_t)len;
@@ -246,55 +181,55 @@ uint64_t RaggedGatherSession::gather(const int64_t* idx, uint64_t batch, uint64_
   set_device();
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (gathers_ > 1 && last_stream_ != stream)   // the workspace is ordered by one stream at a time
-    RG_HIP(hipStreamSynchronize(reinterpret_cast<hipStream_t>(last_stream_)));
+    AMDX_HIP(hipStreamSynchronize(reinterpret_cast<hipStream_t>(last_stream_)));
   last_stream_ = stream;
   if (batch == 0) {
-    RG_HIP(hipMemsetAsync(reinterpret_cast<void*>(out_off), 0, sizeof(uint64_t), st));
+    AMDX_HIP(hipMemsetAsync(reinterpret_cast<void*>(out_off), 0, sizeof(uint64_t), st));
     return 0;
   }
   const int s = slot_;
   slot_ = (slot_ + 1) % kSlots;
-  if (ev_used_[s]) RG_HIP(hipEventSynchronize(ev_[s]));   // the upload that last used this buffer
+  if (ev_used_[s]) AMDX_HIP(hipEventSynchronize(ev_[s]));   // the upload that last used this buffer
   if (h_cap_[s] < batch) {
-    if (h_idx_[s]) RG_HIP(hipHostFree(h_idx_[s]));
+    if (h_idx_[s]) AMDX_HIP(hipHostFree(h_idx_[s]));
     h_idx_[s] = nullptr;
     h_cap_[s] = 0;
     uint64_t cap = 1024;
     while (cap < batch) cap <<= 1;
-    RG_HIP(hipHostMalloc((void**)&h_idx_[s], cap * sizeof(int64_t), hipHostMallocMapped));
+    AMDX_HIP(hipHostMalloc((void**)&h_idx_[s], cap * sizeof(int64_t), hipHostMallocMapped));
     h_cap_[s] = cap;
   }
   std::memcpy(h_idx_[s], idx, batch * sizeof(int64_t));
   RaggedGatherArgs a;
   if (g_index_copy) {
-    RG_HIP(hipMemcpyAsync(d_idx_, h_idx_[s], batch * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    a.idx = d_idx_;
+    AMDX_HIP(hipMemcpyAsync(d_idx_.p, h_idx_[s], batch * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    a.idx = d_idx_.as<int64_t>();
   } else {
     // the plan kernel is the upload: it reads the pinned buffer (one pass, 8 bytes per row)
     void* dp = nullptr;
-    RG_HIP(hipHostGetDevicePointer(&dp, h_idx_[s], 0));
+    AMDX_HIP(hipHostGetDevicePointer(&dp, h_idx_[s], 0));
     a.idx = static_cast<const int64_t*>(dp);
   }
-  a.arena = reinterpret_cast<const uint8_t*>(arena_);
-  a.vtab = d_vtab_;
-  a.recs = static_cast<const RaggedRec*>(d_recs_);
+  a.arena = view_.base();
+  a.vtab = d_vtab_.as<int64_t>();
+  a.recs = d_recs_.as<RaggedRec>();
   a.dst = reinterpret_cast<uint8_t*>(dst);
   a.out_off = reinterpret_cast<uint64_t*>(out_off);
   a.out_len = reinterpret_cast<uint32_t*>(out_len);
-  a.rows = reinterpret_cast<RaggedRow*>(d_rows_);
-  a.chunk_pre = d_chunk_pre_;
+  a.rows = d_rows_.as<RaggedRow>();
+  a.chunk_pre = d_chunk_pre_.as<uint32_t>();
   a.n_rec = n;
   a.row_stride = lay.row_stride;
   a.batch = (uint32_t)batch;
-  a.page_shift = page_shift_;
+  a.page_shift = view_.page_shift;
   a.align = lay.padded ? 1 : lay.align;
   a.max_len = lay.max_len;
   a.padded = lay.padded ? 1 : 0;
   a.pad_value = lay.pad_value;
   a.total_chunks = (uint32_t)chunks;
   a.chunk_shift = chunk_shift;
-  RG_HIP(launch_ragged_gather(a, st));
-  RG_HIP(hipEventRecord(ev_[s], st));   // the pinned buffer is free once the plan has run
+  AMDX_HIP(launch_ragged_gather(a, st));
+  AMDX_HIP(hipEventRecord(ev_[s], st));   // the pinned buffer is free once the plan has run
   ev_used_[s] = true;
   return lay.padded ? batch * lay.row_stride : total;
 }

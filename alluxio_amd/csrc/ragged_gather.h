@@ -15,7 +15,7 @@
 #include <utility>
 #include <vector>
 
-#include "block_store.h"
+#include "paged_view.h"
 
 namespace amdx {
 
@@ -47,7 +47,7 @@ class RaggedGatherSession {
                   uint64_t out_len, const RaggedLayout& lay, int dst_kind, uint64_t stream, uint64_t* data_bytes);
   void close();
   uint64_t records() const { return rec_len_.size(); }
-  bool arena_on_device() const { return arena_device_; }
+  bool arena_on_device() const { return view_.arena_device; }
   uint64_t gathers() const { return gathers_; }
   // A/B: true = the record numbers go to a device buffer with hipMemcpyAsync before the plan;
   // false (default) = the plan kernel reads them from the pinned buffer.
@@ -58,21 +58,13 @@ class RaggedGatherSession {
   void set_device() const;
   BlockStore* store_;
   int64_t session_ = 0;
-  std::vector<int64_t> locks_;
+  BlockPins pins_;              // read locks on every block for the session's lifetime
   int device_ = -1;
   bool on_device_ = false;      // kernels available (a device is in use)
-  bool arena_device_ = false;   // the arena is device memory (not host-readable)
-  int dir_ = -1;
-  uint64_t page_size_ = 0, arena_ = 0;
-  uint32_t page_shift_ = 0;
-  std::vector<int64_t> vtab_;
+  PagedView view_;              // the files, each starting on a fresh virtual page
   std::vector<uint64_t> rec_start_;
   std::vector<uint32_t> rec_len_;
-  int64_t* d_vtab_ = nullptr;
-  void* d_recs_ = nullptr;
-  int64_t* d_idx_ = nullptr;
-  void* d_rows_ = nullptr;
-  uint32_t* d_chunk_pre_ = nullptr;
+  DevBuf d_vtab_, d_recs_, d_idx_, d_rows_, d_chunk_pre_;
   // Pinned index buffers: a ring, so the host may queue this many gathers ahead of the device.
   // Each is sized (and grown) to the batches it carried.
   static constexpr int kSlots = 64;

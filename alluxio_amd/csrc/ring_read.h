@@ -10,7 +10,7 @@
 #include <cstdint>
 #include <vector>
 
-#include "block_store.h"
+#include "paged_view.h"
 
 namespace amdx {
 
@@ -48,20 +48,17 @@ class RingReadSession {
   void set_device() const;
   BlockStore* store_;                       // null for the remote form
   int64_t session_;
-  std::vector<int64_t> blocks_, locks_;
+  std::vector<int64_t> blocks_;
+  BlockPins pins_;                          // read locks on blocks_ for the session's lifetime
   uint64_t file_len_ = 0, buf_, stride_, dst_;
   uint32_t depth_, streams_, cycle_;
   int kind_;
   bool on_device_ = false;
   int device_ = -1;
-  int dir_ = -1;
-  uint64_t page_size_ = 0, arena_ = 0;
-  uint32_t page_shift_ = 0;
-  std::vector<int64_t> ftab_;
+  PagedView view_;                          // the file's pages
   std::vector<uint64_t> c_init_;
   uint64_t footprint_ = 0;   // distinct file bytes one step touches (see finish_init)
-  int64_t* d_ftab_ = nullptr;
-  uint64_t* d_cinit_ = nullptr;
+  DevBuf d_ftab_, d_cinit_;
   uint64_t calls_per_stream_ = 0, total_ = 0, reopens_ = 0;
   bool closed_ = false;
 };

@@ -5,7 +5,8 @@
 // Every page of the arena is its own heap allocation of exactly one page, so a read past a page
 // (or before it) is a heap-buffer-overflow for the sanitizer.  The loop takes one arena base and
 // page numbers, so the lowest allocation is the base and the others are numbered by their
-// distance from it.  Cases: the edge cases of tests/test_delim_index.py.
+// distance from it.  Cases: the edge cases of tests/test_delim_index.py, and the page walk under the
+// loop (for_each_page_run in paged_view_host.h) on its own.
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -65,6 +66,23 @@ void random_text(Arena& a, uint64_t vstart, uint64_t bytes, uint8_t d, uint32_t 
   }
 }
 
+// The pieces must tile [va, va + len) in order, each inside one page, and every byte of them is read.
+void check_runs(Arena& a, uint64_t va, uint64_t len, const char* what) {
+  uint64_t next = 0, sum = 0, want = 0;
+  bool ok = true;
+  for (uint64_t i = 0; i < len; ++i) want += a.at(va + i);
+  amdx::for_each_page_run(a.base, a.vtab.data(), kShift, va, len, [&](const uint8_t* p, uint64_t n, uint64_t done) {
+    const uint64_t first = va + done, last = first + n - 1;
+    ok = ok && done == next && n > 0 && p == &a.at(first) && (first >> kShift) == (last >> kShift);
+    for (uint64_t i = 0; i < n; ++i) sum += p[i];
+    next = done + n;
+  });
+  if (!ok || next != len || sum != want) {
+    std::printf("FAIL page runs, %s: va %llu len %llu\n", what, (unsigned long long)va, (unsigned long long)len);
+    ++failures;
+  }
+}
+
 }  // namespace
 
 int main() {
@@ -100,6 +118,12 @@ int main() {
     check(a, 2 * kPage + 11, 9 * kPage + 123, (uint8_t)d, "delimiter 0x00 / 0xFF");
   }
   check(a, (uint64_t)kPages * kPage - 100, 100, 0xFF, "range ending with the page table");
+  random_text(a, 0, (uint64_t)kPages * kPage, 0x0A, 9, 40);
+  check_runs(a, 3 * kPage + 100, 4 * kPage + 17, "starts and ends mid-page");
+  check_runs(a, 6 * kPage + 4095, 1, "one byte, the last of its page");
+  check_runs(a, 9 * kPage, 1, "one byte, the first of its page");
+  check_runs(a, 11 * kPage + 7, 2 * kPage - 7, "ends on a page's last byte");
+  check_runs(a, 13 * kPage, 0, "empty");
   if (failures) return 1;
   std::printf("delim_index_host_check ok\n");
   return 0;
