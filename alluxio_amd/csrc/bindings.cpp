@@ -1035,6 +1035,16 @@ PYBIND11_MODULE(_C, m) {
           HIP_CHECK(launch_fill_pattern(reinterpret_cast<uint8_t*>(ptr), bytes, seed, word_offset,
                                         reinterpret_cast<hipStream_t>(stream)));
         }, py::arg("ptr"), py::arg("bytes"), py::arg("seed"), py::arg("word_offset") = 0, py::arg("stream") = 0);
+  // store-only roof (tools/store_roof.py): returns the workgroups launched
+  m.def("store_fill", [](uint64_t ptr, uint64_t bytes, uint32_t word, bool nontemporal, unsigned grid,
+                         uint64_t stream) {
+          py::gil_scoped_release rel;
+          unsigned used = 0;
+          HIP_CHECK(launch_store_fill(reinterpret_cast<uint8_t*>(ptr), bytes, word, nontemporal, grid, &used,
+                                      reinterpret_cast<hipStream_t>(stream)));
+          return used;
+        }, py::arg("ptr"), py::arg("bytes"), py::arg("word") = 0, py::arg("nontemporal") = false,
+        py::arg("grid") = 0, py::arg("stream") = 0);
   m.def("evict_select_device", &evict_select_device);
   m.def("page_alloc_device", &page_alloc_device);
   m.def("set_copy_variant", &set_copy_variant, py::arg("variant"), py::arg("grid_cap") = 0);
@@ -1053,6 +1063,11 @@ PYBIND11_MODULE(_C, m) {
     unsigned cap = 0;
     seq_read_variant(&v, &cap);
     return py::make_tuple(v, cap);
+  });
+  // ("fast" | "general", unroll, grid) of the most recent ring-read launch; grid 0: none yet
+  m.def("seq_read_last_launch", [] {
+    const SeqReadLaunch l = seq_read_last_launch();
+    return py::make_tuple(l.fast ? "fast" : "general", l.unroll, l.grid);
   });
   m.def("set_ragged_gather_variant", &set_ragged_gather_variant, py::arg("variant"), py::arg("chunk_shift") = 0);
   m.def("ragged_gather_chunk_shift", &ragged_gather_chunk_shift);

@@ -57,14 +57,34 @@ struct SeqReadArgs {
   uint32_t depth;
   uint32_t page_shift;
   uint64_t footprint = 0;   // distinct file bytes one launch touches (host estimate; 0 = file_len)
+  // launch_base % cycle, for the fast kernel (which never divides); the general kernel reduces
+  // launch_base itself.  Left unset (>= cycle), the launch takes the general kernel.
+  uint64_t base_mod = ~0ull;
 };
 constexpr uint32_t kSeqReadMaxStreams = 8192;
+// Two kernels (kernels.hip): the fast one when buf is a multiple of 1 KiB, the page size is at
+// least 1 KiB and base_mod is set; the general one for every other shape.
 hipError_t launch_seq_read(const SeqReadArgs& a, hipStream_t stream);
-// A/B switch for the sequential-read kernel (bit0: nontemporal ring stores, bit1: unroll 16,
-// bit2: nontemporal loads; -1: the launcher chooses by the launch's footprint).  grid_cap 0 keeps
-// the cap.  The getter returns both as they stand, so a caller can put them back.
+// A/B switch for the sequential-read kernels (bit0: nontemporal ring stores, bit1: unroll 16 — in
+// the general kernel only where depth and buf / 16 are powers of two —, bit2: nontemporal loads;
+// -1: the launcher chooses by the launch's footprint).  grid_cap 0 keeps the cap; the fast kernel's
+// persistent grid (CUs x resident workgroups) is capped by it too.  The getter returns both as
+// they stand, so a caller can put them back.
 void set_seq_read_variant(int variant, unsigned grid_cap);
 void seq_read_variant(int* variant, unsigned* grid_cap);
+// What the most recent launch_seq_read in this process launched (fast = 0: the general kernel;
+// grid = 0: nothing yet).
+struct SeqReadLaunch {
+  int fast;
+  int unroll;
+  unsigned grid;
+};
+SeqReadLaunch seq_read_last_launch();
+// Store-only roof of the ring read: `bytes` (a multiple of 16) at dst (16-byte aligned) are filled
+// with `word` by 16-B vector stores from a persistent grid (grid 0: CUs x resident workgroups),
+// plain or nontemporal.  *grid_used (may be null) = workgroups launched.
+hipError_t launch_store_fill(uint8_t* dst, uint64_t bytes, uint32_t word, bool nontemporal, unsigned grid,
+                             unsigned* grid_used, hipStream_t stream);
 
 // Ragged gather (ragged_gather.hip): `batch` variable-length records, picked by `idx` from a
 // device-resident record index (RaggedRec: virtual byte address and length), are read through a

@@ -128,15 +128,37 @@ hipError_t launch_batched_copy(const CopySeg* segs, int nseg, uint64_t total_chu
 // ---------------------------------------------------------------------------------------------
 // K1': device-cursor multi-stream sequential read (see SeqReadArgs in kernels.h).
 //
-// The flattened index space is (stream, call k, 16-B vector v).  Each workgroup first computes
-// every stream's first call index of this launch (c0[s] = (c_init[s] + launch_base) % cycle) into
-// LDS — one 64-bit modulo per stream instead of per vector — then grid-strides over vectors with
-// 8 independent 16-B loads in flight per lane before the stores (latency hiding for the
-// short, page-table-indirected reads).  Consecutive lanes touch consecutive vectors of the same
-// read, so both the arena gather and the ring store coalesce.  A read whose length is not a
-// multiple of 16 (the last read of a pass) finishes its tail bytes in the owning lane.
+// Two kernels; launch_seq_read picks one per launch and seq_read_last_launch() says which.
+//
+// seq_read_kernel (general: any buf that is a multiple of 16, any page size).  The flattened index
+// space is (stream, call k, 16-B vector v).  Each workgroup first computes every stream's first
+// call index of this launch (c0[s] = (c_init[s] + launch_base) % cycle) into LDS — one 64-bit
+// modulo per stream instead of per vector — then grid-strides over vectors, UNROLL of them per lane
+// and trip.  Call index, EOF test and page-table lookup are per lane, and every sub-iteration's
+// 16-B data load waits for its own page-table load, which also waits for the data load before it:
+// a lane has ONE data load in flight, the UNROLL stores follow the last of them.  Consecutive
+// lanes touch consecutive vectors of the same read, so both the arena gather and the ring store
+// coalesce.  A read whose length is not a multiple of 16 (the last read of a pass) finishes its
+// tail bytes in the owning lane.
+//
+// seq_read_fast_kernel (buf a multiple of 1 KiB, pages of at least 1 KiB).  The index space is
+// (stream, call k, 1 KiB chunk of the call's slot); a chunk is 64 lanes x one 16-B vector and never
+// straddles a page.  A wave owns U consecutive chunks per trip of a persistent grid-stride loop
+// (grid = CUs x resident workgroups, capped by grid_cap).  Everything that decides addresses —
+// stream, call, call index c, EOF, the page lookup, the source and ring bases — is worked out from
+// wave-uniform values (blockIdx, the wave id through readfirstlane, kernel arguments), so it lives
+// in SGPRs and c_init[s] / ftab[page] come through scalar loads; a lane only adds lane * 16.  No
+// LDS, no barrier and no 64-bit modulo: the host passes launch_base % cycle and c_init[s] < cycle,
+// so c is two adds and two compare-subtracts; a launch with depth > cycle (several passes inside
+// one launch) runs a second instantiation of the loop that first reduces k by a 32-bit modulo.
+// Consecutive chunks are consecutive calls of one stream, so a trip that stays inside one stream's
+// ring, one page and the file is contiguous in both: it is resolved once and issues its U 16-B
+// loads back to back, then its U stores.  Any other trip (a page or stream boundary, an EOF call,
+// the end of a pass or of the index space) resolves each chunk by itself: see seq_fast_loop.
 // ---------------------------------------------------------------------------------------------
 constexpr int kSeqThreads = 256;
+constexpr uint32_t kSeqChunkShift = 10;                 // fast path: 1 KiB = 64 lanes x 16 B
+constexpr uint32_t kSeqChunk = 1u << kSeqChunkShift;
 
 // POW2: vectors-per-read and depth are powers of two -> index math is shifts/masks (the common
 // case: 4 KiB reads x 256 calls); otherwise 64-bit division.  SP: store policy of the ring
@@ -205,6 +227,136 @@ __global__ __launch_bounds__(kSeqThreads) void seq_read_kernel(SeqReadArgs a, ui
   }
 }
 
+// Stream, call and chunk-of-the-slot of chunk q (q < streams * depth * cpr), all wave-uniform.
+template <bool POW2>
+__device__ __forceinline__ void seq_split(const SeqReadArgs& a, uint64_t q, uint64_t cpr, uint32_t cpr_shift,
+                                          uint32_t depth_shift, uint32_t* s, uint32_t* k, uint64_t* ci) {
+  if constexpr (POW2) {
+    const uint64_t rd = q >> cpr_shift;
+    *ci = q & (cpr - 1);
+    *s = (uint32_t)(rd >> depth_shift);
+    *k = (uint32_t)(rd & (a.depth - 1));
+  } else {
+    const uint64_t rd = q / cpr;
+    *ci = q - rd * cpr;
+    *s = (uint32_t)(rd / a.depth);
+    *k = (uint32_t)(rd - (uint64_t)*s * a.depth);
+  }
+}
+
+// Call index of a stream's k-th call of this launch, c0 = c_init[s]: c0, base_mod and (after the
+// MULTI reduction) k are all below cycle, so two compare-subtracts do.  MULTI: depth > cycle, a
+// launch holds several passes and k needs a real (32-bit, wave-uniform) modulo first.
+template <bool MULTI>
+__device__ __forceinline__ uint64_t seq_call_index(const SeqReadArgs& a, uint64_t c0, uint32_t k) {
+  if constexpr (MULTI) k %= a.cycle;
+  uint64_t c = c0 + a.base_mod;
+  c = c >= a.cycle ? c - a.cycle : c;
+  c += k;
+  return c >= a.cycle ? c - a.cycle : c;
+}
+
+// The body of the fast kernel (the kernel picks MULTI once, at its top).  A trip owns the U
+// consecutive chunks from g * U on and resolves the first of them.  Where all U lie in one stream's
+// ring, before the file's end (so none is an EOF call) and in one page, file and ring are both
+// contiguous over the trip: one page lookup, and the U loads and U stores differ by u KiB.  Any
+// other trip — a page or stream boundary inside it, an EOF call, the end of a pass or of the index
+// space — resolves every chunk by itself, four at a time, in straight-line stages so that the
+// scalar loads of a stage go out together and the four data loads follow each other before the
+// four stores: n[u] = bytes to move, 1024, the tail of a pass, or 0; a chunk that moves nothing
+// looks up stream 0 / page 0, so every load stays inside its table.  Lanes wholly before n[u] use
+// the vector, the lane that holds the end finishes the tail bytes.
+template <bool POW2, int U, int SP, int LP, bool MULTI>
+__device__ __forceinline__ void seq_fast_loop(const SeqReadArgs& a, const uint8_t* __restrict__ arena,
+                                              const int64_t* __restrict__ ftab,
+                                              const uint64_t* __restrict__ c_init, uint8_t* __restrict__ dst,
+                                              uint32_t cpr_shift, uint32_t depth_shift) {
+  constexpr uint32_t kWaves = kSeqThreads / 64;
+  constexpr uint64_t kTrip = (uint64_t)U * kSeqChunk;
+  constexpr int kGen = 4;                                // chunks per batch of the general path
+  const uint32_t lane16 = (threadIdx.x & 63u) * 16u;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint64_t cpr = a.buf >> kSeqChunkShift;          // chunks per read slot
+  const uint64_t per_stream = (uint64_t)a.depth * cpr;
+  const uint64_t nchunks = (uint64_t)a.streams * per_stream;
+  const uint64_t ngroups = (nchunks + U - 1) / U;        // U is a power of two: a shift
+  const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
+  const uint64_t pmask = (1ull << a.page_shift) - 1;
+  for (uint64_t g = (uint64_t)blockIdx.x * kWaves + wave; g < ngroups; g += nwaves) {
+    uint32_t s0, k0;
+    uint64_t ci0;
+    seq_split<POW2>(a, g * U, cpr, cpr_shift, depth_shift, &s0, &k0, &ci0);
+    const uint64_t w0 = (uint64_t)k0 * cpr + ci0;        // chunk of the stream's ring
+    const uint64_t off0 = seq_call_index<MULTI>(a, c_init[s0], k0) * a.buf + (ci0 << kSeqChunkShift);
+    u32x4 v[U];
+    // the EOF call starts at or past file_len, so the second test also says "no EOF call inside"
+    if (w0 + U <= per_stream && off0 + kTrip <= a.file_len && (off0 & pmask) + kTrip <= pmask + 1) {
+      const uint64_t page = (uint64_t)ftab[off0 >> a.page_shift];
+      const u32x4* sp = reinterpret_cast<const u32x4*>(arena + (page << a.page_shift) + (off0 & pmask) + lane16);
+      u32x4* dp = reinterpret_cast<u32x4*>(dst + (uint64_t)s0 * a.stream_stride + (w0 << kSeqChunkShift) + lane16);
+#pragma unroll
+      for (int u = 0; u < U; ++u) v[u] = ld16<LP>(sp + u * (kSeqChunk / 16));
+#pragma unroll
+      for (int u = 0; u < U; ++u) st16<SP>(dp + u * (kSeqChunk / 16), v[u]);
+      continue;
+    }
+    // not unrolled: kGen chunks at a time keep this rare path's registers below the hot path's
+#pragma unroll 1
+    for (int h = 0; h < U; h += kGen) {
+      uint64_t dof[kGen], c0[kGen], sof[kGen];
+      uint32_t k[kGen], n[kGen];
+      int64_t page[kGen];
+#pragma unroll
+      for (int u = 0; u < kGen; ++u) {                   // stream, call, ring offset, c_init[s]
+        const uint64_t q = g * U + h + u;
+        n[u] = q < nchunks ? kSeqChunk : 0;
+        uint32_t s;
+        uint64_t ci;
+        seq_split<POW2>(a, q < nchunks ? q : 0, cpr, cpr_shift, depth_shift, &s, &k[u], &ci);
+        sof[u] = ci << kSeqChunkShift;
+        dof[u] = (uint64_t)s * a.stream_stride + (uint64_t)k[u] * a.buf + sof[u];
+        c0[u] = c_init[s];
+      }
+#pragma unroll
+      for (int u = 0; u < kGen; ++u) {                   // call index, file offset, bytes, ftab[page]
+        const uint64_t c = seq_call_index<MULTI>(a, c0[u], k[u]);
+        const uint64_t off = c * a.buf + sof[u];
+        const bool data = c != a.cycle - 1 && off < a.file_len;   // not the EOF call, not past the end
+        const uint64_t left = data ? a.file_len - off : 0;
+        n[u] = left < n[u] ? (uint32_t)left : n[u];
+        sof[u] = data ? off : 0;
+        page[u] = ftab[sof[u] >> a.page_shift];
+      }
+#pragma unroll
+      for (int u = 0; u < kGen; ++u) {                   // source address; the loads, back to back
+        const uint8_t* src = arena + ((uint64_t)page[u] << a.page_shift) + (sof[u] & pmask);
+        sof[u] = reinterpret_cast<uint64_t>(src);
+        if (lane16 + 16 <= n[u]) v[u] = ld16<LP>(reinterpret_cast<const u32x4*>(src + lane16));
+      }
+#pragma unroll
+      for (int u = 0; u < kGen; ++u) {
+        if (lane16 + 16 <= n[u]) {
+          st16<SP>(reinterpret_cast<u32x4*>(dst + dof[u] + lane16), v[u]);
+        } else if (lane16 < n[u]) {
+          // the lane that holds the end of the pass: its tail bytes (same page, a chunk does not straddle)
+          const uint8_t* src = reinterpret_cast<const uint8_t*>(sof[u]);
+          for (uint32_t b = lane16; b < n[u]; ++b) dst[dof[u] + b] = src[b];
+        }
+      }
+    }
+  }
+}
+
+// The pointers are separate __restrict__ parameters (not read from SeqReadArgs) so that the
+// compiler knows the ring stores cannot change c_init or ftab and keeps their loads scalar.
+template <bool POW2, int U, int SP, int LP>
+__global__ __launch_bounds__(kSeqThreads) void seq_read_fast_kernel(
+    SeqReadArgs a, const uint8_t* __restrict__ arena, const int64_t* __restrict__ ftab,
+    const uint64_t* __restrict__ c_init, uint8_t* __restrict__ dst, uint32_t cpr_shift, uint32_t depth_shift) {
+  if (a.depth > a.cycle) seq_fast_loop<POW2, U, SP, LP, true>(a, arena, ftab, c_init, dst, cpr_shift, depth_shift);
+  else seq_fast_loop<POW2, U, SP, LP, false>(a, arena, ftab, c_init, dst, cpr_shift, depth_shift);
+}
+
 // 0: cached stores, 1: nontemporal stores, +2: unroll 16, +4: nontemporal loads; -1 (default): auto —
 // nontemporal LOADS once a launch streams >= 128 MiB of distinct file bytes (half the 256 MB MALL):
 // those bytes are read once, so streaming them past L2/MALL leaves the caches to the ring writes
@@ -224,11 +376,63 @@ void seq_read_variant(int* variant, unsigned* grid_cap) {
   *grid_cap = g_seq_grid_cap;
 }
 
+static SeqReadLaunch g_seq_last;   // what the last launch_seq_read chose (all zero: none yet)
+
+SeqReadLaunch seq_read_last_launch() { return g_seq_last; }
+
 static inline bool is_pow2(uint64_t x) { return x && !(x & (x - 1)); }
 static inline uint32_t log2u(uint64_t x) {
   uint32_t s = 0;
   while ((1ull << s) < x) ++s;
   return s;
+}
+
+// A persistent grid: the current device's CUs x the workgroups of `kernel` (kSeqThreads threads,
+// no LDS) that one CU holds.  Asked of the runtime once per device and kernel; `cached` is the
+// kernel's own table.
+constexpr int kMaxDev = 64;
+template <typename K>
+static hipError_t resident_workgroups(K kernel, unsigned (&cached)[kMaxDev], unsigned* out) {
+  static std::mutex mu;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (dev < 0 || dev >= kMaxDev) return hipErrorInvalidDevice;
+  std::lock_guard<std::mutex> lk(mu);
+  if (!cached[dev]) {
+    int cus = 0, per_cu = 0;
+    if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
+    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kSeqThreads, 0)) != hipSuccess) return e;
+    if (cus < 1 || per_cu < 1) return hipErrorInvalidValue;
+    cached[dev] = (unsigned)cus * (unsigned)per_cu;
+  }
+  *out = cached[dev];
+  return hipSuccess;
+}
+
+template <bool P2, int U, int SP, int LP>
+static hipError_t seq_fast_resident(unsigned* out) {
+  static unsigned cached[kMaxDev] = {};
+  return resident_workgroups(seq_read_fast_kernel<P2, U, SP, LP>, cached, out);
+}
+
+template <bool P2, int U, int SP, int LP>
+static hipError_t launch_seq_fast(const SeqReadArgs& a, hipStream_t stream) {
+  unsigned resident = 0;
+  const hipError_t e = seq_fast_resident<P2, U, SP, LP>(&resident);
+  if (e != hipSuccess) return e;
+  const uint64_t cpr = a.buf >> kSeqChunkShift;
+  const uint64_t nchunks = (uint64_t)a.streams * a.depth * cpr;
+  const uint64_t ngroups = (nchunks + U - 1) / U;
+  constexpr uint64_t kWaves = kSeqThreads / 64;
+  uint64_t blocks = (ngroups + kWaves - 1) / kWaves;
+  if (blocks > resident) blocks = resident;
+  if (blocks > g_seq_grid_cap) blocks = g_seq_grid_cap;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL((seq_read_fast_kernel<P2, U, SP, LP>), dim3((unsigned)blocks), dim3(kSeqThreads), 0, stream,
+                     a, a.arena, a.ftab, a.c_init, a.dst, log2u(cpr), log2u(a.depth));
+  g_seq_last = SeqReadLaunch{1, U, (unsigned)blocks};
+  return hipGetLastError();
 }
 
 hipError_t launch_seq_read(const SeqReadArgs& a, hipStream_t stream) {
@@ -241,6 +445,22 @@ hipError_t launch_seq_read(const SeqReadArgs& a, hipStream_t stream) {
   const uint64_t fp = a.footprint ? a.footprint : a.file_len;
   const int var = g_seq_variant >= 0 ? g_seq_variant : (fp >= (128ull << 20) ? 4 : 0);
   const int unroll = (var & 2) ? 16 : 8;
+  // Fast path: whole 1 KiB chunks that never straddle a page, and the reduced launch base the
+  // kernel's compare-subtracts rely on.  Everything else takes the general kernel below.
+  if ((a.buf & (kSeqChunk - 1)) == 0 && a.page_shift >= kSeqChunkShift && a.base_mod < a.cycle) {
+    const bool p2 = is_pow2(a.buf >> kSeqChunkShift) && is_pow2(a.depth);
+    const int sel = (p2 ? 8 : 0) | (unroll == 16 ? 4 : 0) | ((var & 1) ? 2 : 0) | ((var & 4) ? 1 : 0);
+    switch (sel) {
+#define AMDX_FAST(N, P2, U, SP, LP) case N: return launch_seq_fast<P2, U, SP, LP>(a, stream)
+      AMDX_FAST(0, false, 8, 0, 0); AMDX_FAST(1, false, 8, 0, 1); AMDX_FAST(2, false, 8, 1, 0);
+      AMDX_FAST(3, false, 8, 1, 1); AMDX_FAST(4, false, 16, 0, 0); AMDX_FAST(5, false, 16, 0, 1);
+      AMDX_FAST(6, false, 16, 1, 0); AMDX_FAST(7, false, 16, 1, 1); AMDX_FAST(8, true, 8, 0, 0);
+      AMDX_FAST(9, true, 8, 0, 1); AMDX_FAST(10, true, 8, 1, 0); AMDX_FAST(11, true, 8, 1, 1);
+      AMDX_FAST(12, true, 16, 0, 0); AMDX_FAST(13, true, 16, 0, 1); AMDX_FAST(14, true, 16, 1, 0);
+      default: AMDX_FAST(15, true, 16, 1, 1);
+#undef AMDX_FAST
+    }
+  }
   uint64_t blocks = (nvec + (uint64_t)kSeqThreads * unroll - 1) / ((uint64_t)kSeqThreads * unroll);
   if (blocks > g_seq_grid_cap) blocks = g_seq_grid_cap;
   if (blocks < 1) blocks = 1;
@@ -264,6 +484,54 @@ hipError_t launch_seq_read(const SeqReadArgs& a, hipStream_t stream) {
     else { if (sp) AMDX_SEQ(false, 8, 1, 0); else AMDX_SEQ(false, 8, 0, 0); }
   }
 #undef AMDX_SEQ
+  g_seq_last = SeqReadLaunch{0, p2 ? unroll : 8, (unsigned)blocks};
+  return hipGetLastError();
+}
+
+// Store-only roof of the ring read (tools/store_roof.py): fills `bytes` at dst with one 32-bit word
+// through 16-B vector stores, a wave storing 8 consecutive KiB per trip of a persistent grid, as
+// the fast kernel's contiguous trips do, with no load at all.
+template <int SP>
+__global__ __launch_bounds__(kSeqThreads) void store_fill_kernel(u32x4* __restrict__ dst, uint64_t nvec,
+                                                                 uint32_t word) {
+  constexpr uint32_t kWaves = kSeqThreads / 64;
+  constexpr uint64_t kTripVec = 8 * (kSeqChunk / 16);    // vectors per trip
+  const u32x4 v = {word, word, word, word};
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint64_t trips = nvec / kTripVec;
+  const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
+  for (uint64_t g = (uint64_t)blockIdx.x * kWaves + wave; g < trips; g += nwaves) {
+    u32x4* p = dst + g * kTripVec + lane;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) st16<SP>(p + u * (kSeqChunk / 16), v);
+  }
+  for (uint64_t i = trips * kTripVec + (uint64_t)blockIdx.x * kSeqThreads + threadIdx.x; i < nvec;
+       i += (uint64_t)gridDim.x * kSeqThreads)
+    st16<SP>(dst + i, v);
+}
+
+hipError_t launch_store_fill(uint8_t* dst, uint64_t bytes, uint32_t word, bool nontemporal, unsigned grid,
+                             unsigned* grid_used, hipStream_t stream) {
+  if (((uint64_t)dst & 15) || (bytes & 15)) return hipErrorInvalidValue;
+  if (grid_used) *grid_used = 0;
+  if (bytes == 0) return hipSuccess;
+  static unsigned cached[2][kMaxDev] = {};
+  unsigned resident = 0;
+  const hipError_t e = nontemporal ? resident_workgroups(store_fill_kernel<1>, cached[1], &resident)
+                                   : resident_workgroups(store_fill_kernel<0>, cached[0], &resident);
+  if (e != hipSuccess) return e;
+  const uint64_t nvec = bytes >> 4;
+  uint64_t blocks = grid ? grid : resident;
+  const uint64_t need = (nvec + kSeqThreads - 1) / kSeqThreads;
+  if (blocks > need) blocks = need;
+  if (nontemporal)
+    hipLaunchKernelGGL(store_fill_kernel<1>, dim3((unsigned)blocks), dim3(kSeqThreads), 0, stream,
+                       reinterpret_cast<u32x4*>(dst), nvec, word);
+  else
+    hipLaunchKernelGGL(store_fill_kernel<0>, dim3((unsigned)blocks), dim3(kSeqThreads), 0, stream,
+                       reinterpret_cast<u32x4*>(dst), nvec, word);
+  if (grid_used) *grid_used = (unsigned)blocks;
   return hipGetLastError();
 }
 

@@ -44,6 +44,8 @@ void RingReadSession::check_shape() {
   const uint64_t calls = (file_len_ + buf_ - 1) / buf_;
   if (calls + 1 >= (1ull << 32)) throw StoreError(kErrInvalidArgument, "ring read: too many calls per pass");
   cycle_ = (uint32_t)(calls + 1);
+  full_passes_ = depth_ / cycle_;
+  rem_calls_ = depth_ % cycle_;
 }
 
 void RingReadSession::set_device() const {
@@ -63,6 +65,7 @@ void RingReadSession::finish_init(const std::vector<uint64_t>& start_offsets) {
   std::sort(starts.begin(), starts.end());
   const uint64_t distinct = (uint64_t)(std::unique(starts.begin(), starts.end()) - starts.begin());
   footprint_ = std::min<uint64_t>(file_len_, distinct * depth_ * buf_);
+  lockstep_ = distinct == 1;
   if (on_device_) {
     if (buf_ & 15 || stride_ & 15 || dst_ & 15)
       throw StoreError(kErrInvalidArgument, "ring read: buffer size, stride and ring base must be 16-byte aligned");
@@ -89,9 +92,16 @@ void RingReadSession::close() {
   pins_.release();
 }
 
-uint64_t RingReadSession::bytes_before(uint64_t g) const {
-  const uint64_t passes = g / cycle_, rem = g % cycle_;
-  return passes * file_len_ + std::min<uint64_t>(rem * buf_, file_len_);
+uint64_t RingReadSession::step_bytes(uint64_t c0, uint64_t* eofs) const {
+  // depth = full_passes_ * cycle + rem_calls_: every full pass reads the file once and ends in one
+  // EOF call; the other rem_calls_ calls are [c0, c1) with c1 < 2 * cycle
+  auto before = [this](uint64_t x) {                     // bytes of calls [0, x), x < 2 * cycle
+    return x < cycle_ ? std::min<uint64_t>(x * buf_, file_len_)
+                      : file_len_ + std::min<uint64_t>((x - cycle_) * buf_, file_len_);
+  };
+  const uint64_t c1 = c0 + rem_calls_;
+  *eofs = (uint64_t)full_passes_ + (c1 >= cycle_ ? 1 : 0);
+  return (uint64_t)full_passes_ * file_len_ + before(c1) - before(c0);
 }
 
 uint64_t RingReadSession::step(uint64_t stream, uint64_t* eofs) {
@@ -108,6 +118,7 @@ uint64_t RingReadSession::step(uint64_t stream, uint64_t* eofs) {
     a.file_len = file_len_;
     a.buf = buf_;
     a.launch_base = base;
+    a.base_mod = base_mod_;
     a.cycle = cycle_;
     a.streams = streams_;
     a.depth = depth_;
@@ -121,7 +132,7 @@ uint64_t RingReadSession::step(uint64_t stream, uint64_t* eofs) {
     for (uint32_t s = 0; s < streams_; ++s)
       for (uint32_t k = 0; k < depth_; ++k) {
         auto [off, len] = std::pair<uint64_t, uint64_t>(0, 0);
-        const uint64_t c = (c_init_[s] + base + k) % cycle_;
+        const uint64_t c = (c_init_[s] + base_mod_ + k) % cycle_;
         if (c == cycle_ - 1) continue;
         off = c * buf_;
         len = std::min(buf_, file_len_ - off);
@@ -130,13 +141,25 @@ uint64_t RingReadSession::step(uint64_t stream, uint64_t* eofs) {
                           [d](const uint8_t* p, uint64_t n, uint64_t done) { std::memcpy(d + done, p, n); });
       }
   }
+  // accounting without a division: c_init_[s] and base_mod_ are both below cycle
+  auto first_call = [this](uint32_t s) {
+    const uint64_t c = c_init_[s] + base_mod_;
+    return c >= cycle_ ? c - cycle_ : c;
+  };
   uint64_t bytes = 0, eof = 0;
-  for (uint32_t s = 0; s < streams_; ++s) {
-    const uint64_t g0 = c_init_[s] + base, g1 = g0 + depth_;
-    bytes += bytes_before(g1) - bytes_before(g0);
-    eof += g1 / cycle_ - g0 / cycle_;
+  if (lockstep_) {
+    bytes = step_bytes(first_call(0), &eof) * streams_;
+    eof *= streams_;
+  } else {
+    for (uint32_t s = 0; s < streams_; ++s) {
+      uint64_t e = 0;
+      bytes += step_bytes(first_call(s), &e);
+      eof += e;
+    }
   }
   calls_per_stream_ += depth_;
+  base_mod_ += rem_calls_;                                // (base + depth) % cycle
+  if (base_mod_ >= cycle_) base_mod_ -= cycle_;
   total_ += bytes;
   reopens_ += eof;
   if (store_) store_->access_blocks(blocks_);

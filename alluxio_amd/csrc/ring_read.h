@@ -42,7 +42,9 @@ class RingReadSession {
   uint64_t file_len() const { return file_len_; }
 
  private:
-  uint64_t bytes_before(uint64_t g) const;  // bytes read by calls [0, g) of one stream
+  // bytes and EOF calls of `depth` consecutive calls of one stream whose first call index is
+  // c0 < cycle; no division (full_passes_ and rem_calls_ are fixed at construction)
+  uint64_t step_bytes(uint64_t c0, uint64_t* eofs) const;
   void check_shape();
   void finish_init(const std::vector<uint64_t>& start_offsets);
   void set_device() const;
@@ -58,6 +60,9 @@ class RingReadSession {
   PagedView view_;                          // the file's pages
   std::vector<uint64_t> c_init_;
   uint64_t footprint_ = 0;   // distinct file bytes one step touches (see finish_init)
+  bool lockstep_ = false;    // every stream starts at the same call: one accounting serves all
+  uint32_t full_passes_ = 0, rem_calls_ = 0;   // depth / cycle, depth % cycle
+  uint64_t base_mod_ = 0;    // calls_per_stream_ % cycle, carried from step to step
   DevBuf d_ftab_, d_cinit_;
   uint64_t calls_per_stream_ = 0, total_ = 0, reopens_ = 0;
   bool closed_ = false;

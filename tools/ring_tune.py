@@ -48,6 +48,7 @@ def main():
             readers[d] = (RingStreamReader(fs, "/tune", ring, start_offsets=starts), ring)
         combos = [(d, int(v), int(cap)) for d in readers for v in a.variants.split(",") for cap in a.caps.split(",")]
         t = {k: [] for k in combos}
+        ran = {}
         for _ in range(a.rounds):
             for k in combos:
                 d, v, cap = k
@@ -61,8 +62,9 @@ def main():
                     r.step()
                 torch.cuda.synchronize()
                 t[k].append((r.rs.total_bytes - b0) / (time.perf_counter() - t0) / 1e9)
+                ran[k] = C.seq_read_last_launch()         # (kernel, unroll, grid) of this combination
         for k in combos:
-            row = {"file_size": fsize, "stagger": a.stagger, "depth": k[0], "variant": k[1], "grid_cap": k[2], "GBps_median": round(statistics.median(t[k]), 1),
+            row = {"file_size": fsize, "stagger": a.stagger, "depth": k[0], "variant": k[1], "grid_cap": k[2], "kernel": ran[k][0], "unroll": ran[k][1], "grid": ran[k][2], "GBps_median": round(statistics.median(t[k]), 1),
                    "GBps_max": round(max(t[k]), 1)}
             res.append(row)
             print(json.dumps(row), flush=True)
