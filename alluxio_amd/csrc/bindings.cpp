@@ -17,6 +17,7 @@
 #include "ragged_gather.h"
 #include "delim_index.h"
 #include "field_parse.h"
+#include "text_column.h"
 #include "kernels.h"
 #include "seg_ring.h"
 #include "frame_rpc.h"
@@ -706,6 +707,29 @@ PYBIND11_MODULE(_C, m) {
         py::arg("stream") = 0);
   m.def("field_parse_launches", &field_parse_launches);
 
+  // ---- text columns from spans (text_column.cpp) ---------------------------------------------
+  // start (int64), length (int32), status (uint8, or 0: none) are a span column's arrays.  measure
+  // writes out_len (int32, n); emit takes offsets (int64, n + 1: the exclusive scan of out_len) and
+  // writes the packed bytes.  device < 0: host memory, done on return; otherwise queued on `stream`.
+  m.def("text_measure_raw",
+        [](uint64_t data, uint64_t data_bytes, uint64_t start, uint64_t length, uint64_t status, uint64_t n, int device,
+           int64_t quote, uint64_t out_len, uint64_t stream) {
+          py::gil_scoped_release rel;
+          text_measure_raw(data, data_bytes, start, length, status, n, device, quote, out_len, stream);
+        },
+        py::arg("data"), py::arg("data_bytes"), py::arg("start"), py::arg("length"), py::arg("status"), py::arg("n"),
+        py::arg("device"), py::arg("quote"), py::arg("out_len"), py::arg("stream") = 0);
+  m.def("text_emit_raw",
+        [](uint64_t data, uint64_t data_bytes, uint64_t start, uint64_t length, uint64_t status, uint64_t n, int device,
+           int64_t quote, uint64_t offsets, uint64_t out, uint64_t out_bytes, uint64_t stream) {
+          py::gil_scoped_release rel;
+          text_emit_raw(data, data_bytes, start, length, status, n, device, quote, offsets, out, out_bytes, stream);
+        },
+        py::arg("data"), py::arg("data_bytes"), py::arg("start"), py::arg("length"), py::arg("status"), py::arg("n"),
+        py::arg("device"), py::arg("quote"), py::arg("offsets"), py::arg("out"), py::arg("out_bytes"),
+        py::arg("stream") = 0);
+  m.def("text_column_launches", &text_column_launches);
+
   // ---- native S3 data path (http_blob.cpp) --------------------------------------------------
   py::class_<BlobServer>(m, "BlobServer")
       .def(py::init<const std::string&, const std::string&, int>(), py::arg("root"), py::arg("host") = "127.0.0.1",
@@ -1078,6 +1102,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("delim_quote_variant", &delim_quote_variant);
   m.def("set_field_parse_variant", &set_field_parse_variant, py::arg("variant"));
   m.def("field_parse_variant", &field_parse_variant);
+  m.def("set_text_column_variant", &set_text_column_variant, py::arg("variant"));
+  m.def("text_column_variant", &text_column_variant);
   m.def("set_page_gather_chunk_variant", &set_page_gather_chunk_variant, py::arg("variant"));
   m.attr("COPY_CHUNK") = kCopyChunk;
 }

@@ -12,6 +12,7 @@
 #include <cstdint>
 
 #include "field_parse_host.h"
+#include "text_column_host.h"
 
 namespace amdx {
 
@@ -209,6 +210,18 @@ hipError_t launch_field_parse(const FieldParseArgs& a, hipStream_t stream);
 // 0 = one lane per row (a serial byte walk), 1 (default) = sixteen lanes per row over 256-byte steps.
 void set_field_parse_variant(int variant);
 int field_parse_variant();
+
+// Text columns (text_column.hip): the bytes of span values with doubled quotes collapsed, packed.
+// TextColumnArgs and the rule are in text_column_host.h.  measure writes out_len[r]; emit, given
+// the exclusive scan of out_len in offsets, writes value r at out[offsets[r] ...] and never outside
+// [offsets[r], offsets[r + 1]) cut to [0, out_bytes).  One launch each, no workspace, no atomics;
+// only bytes of live values are read.  The launchers re-check the quote (-1..255), n <= 2^31 and
+// the pointers and refuse with hipErrorInvalidValue.
+hipError_t launch_text_measure(const TextColumnArgs& a, hipStream_t stream);
+hipError_t launch_text_emit(const TextColumnArgs& a, hipStream_t stream);
+// 0 = one lane per value (a serial byte walk), 1 (default) = sixteen lanes per value over 256-byte steps.
+void set_text_column_variant(int variant);
+int text_column_variant();
 
 // CRC32C (Castagnoli, reflected, init/xorout 0xFFFFFFFF) of `n` equal-length pieces
 // (piece i = base + i*piece_bytes, last may be shorter: total_bytes).  `out` device array.

@@ -8,9 +8,10 @@ The rule (``csrc/field_parse_host.h`` has it in full): a row is its bytes withou
 (and without the ``\\r`` before a ``\\n``); a separator splits where an even number of quote bytes
 precedes it in the row; a field loses one pair of enclosing quotes, then blanks and tabs at both
 ends.  Doubled quotes inside stay as they are: a ``span`` column returns them raw and a numeric
-column calls them malformed.
+column calls them malformed; a ``text`` column undoes them (:func:`extract_text`).
 
-Column types: ``"span"`` (``start`` into the batch's flat data and ``length``), ``"int64"``,
+Column types: ``"span"`` (``start`` into the batch's flat data and ``length``), ``"text"`` (the
+unquoted bytes of all values packed into ``data``, with ``offsets`` and ``length``), ``"int64"``,
 ``"int32"``, ``"float64"``, ``"float32"``.  Status per value: 0 valid, 1 no value (field absent
 or empty), 2 malformed or out of range, 3 deferred.  The device parses a float itself only where
 one correctly rounded fp64 operation is exact (at most 19 significant digits, mantissa at most
@@ -24,19 +25,19 @@ import numpy as np
 
 from .dataset import DeviceBatchLoader, IndexedRecordDataset, RaggedBatch, build_delimited_index
 
-SPAN, INT64, INT32, FLOAT64, FLOAT32 = range(5)
-_TYPES = {"span": SPAN, "int64": INT64, "int32": INT32, "float64": FLOAT64, "float32": FLOAT32,
-          "int": INT64, "float": FLOAT64, "str": SPAN}
+SPAN, INT64, INT32, FLOAT64, FLOAT32, TEXT = range(6)
+_TYPES = {"span": SPAN, "int64": INT64, "int32": INT32, "float64": FLOAT64, "float32": FLOAT32, "text": TEXT,
+          "int": INT64, "float": FLOAT64, "str": SPAN, "bytes": TEXT}
 _MAX_COLS = 32
 
 
 def _type_code(dtype) -> int:
-    # a name, a torch / numpy dtype (torch.int64, np.float32) or one of int, float, str
+    # a name, a torch / numpy dtype (torch.int64, np.float32) or one of int, float, str, bytes
     name = dtype.__name__ if isinstance(dtype, type) else str(dtype).replace("torch.", "")
     try:
         return _TYPES[name]
     except KeyError:
-        raise ValueError(f"unknown column type {dtype!r}: one of span, int64, int32, float64, float32") from None
+        raise ValueError(f"unknown column type {dtype!r}: one of span, text, int64, int32, float64, float32") from None
 
 
 def _one_byte(x, what: str) -> int:
@@ -56,20 +57,44 @@ def _scalars(sep, quote, terminator):
 
 class Column:
     """One parsed column: ``values`` and ``status``; a span column has ``start`` and ``length``
-    instead of ``values``."""
+    instead of ``values``; a text column has ``data`` (the bytes of all values, packed), ``offsets``
+    (rows + 1: value r is ``data[offsets[r]:offsets[r + 1]]``) and ``length``."""
 
-    __slots__ = ("name", "field", "type", "values", "start", "length", "status")
+    __slots__ = ("name", "field", "type", "values", "start", "length", "status", "data", "offsets")
 
-    def __init__(self, name, field, type_, values, length, status):
+    def __init__(self, name, field, type_, values, length, status, data=None, offsets=None):
         self.name, self.field, self.type = name, field, type_
         self.status = status
+        self.data, self.offsets = data, offsets
         if type_ == SPAN:
+            self.values, self.start, self.length = None, values, length
+        elif type_ == TEXT:                             # values: the span's start until the text is extracted
             self.values, self.start, self.length = None, values, length
         else:
             self.values, self.start, self.length = values, None, None
 
     def _tensors(self):
+        if self.type == TEXT:
+            return (self.data, self.offsets, self.length, self.status)
         return (self.start, self.length, self.status) if self.type == SPAN else (self.values, self.status)
+
+    def tolist(self) -> list:
+        """The column on the host, ``None`` where the status is not 0: ``bytes`` for a text column
+        (one device-to-host copy for the whole column), numbers for a numeric one, ``(start,
+        length)`` for a span."""
+        import torch
+        if self.type == TEXT:
+            n, nb = int(self.status.numel()), int(self.data.numel())
+            blob = torch.cat([self.data, self.offsets.view(torch.uint8), self.status]).cpu().numpy()
+            cuts = blob[nb:nb + 8 * (n + 1)].view(np.int64).tolist()
+            text, st = blob[:nb].tobytes(), blob[nb + 8 * (n + 1):].tolist()
+            return [text[cuts[r]:cuts[r + 1]] if st[r] == 0 else None for r in range(n)]
+        st = self.status.cpu().tolist()
+        if self.type == SPAN:
+            vals = list(zip(self.start.cpu().tolist(), self.length.cpu().tolist()))
+        else:
+            vals = self.values.cpu().tolist()
+        return [v if s == 0 else None for v, s in zip(vals, st)]
 
     def __repr__(self):
         kind = [k for k, v in _TYPES.items() if v == self.type][0]
@@ -105,11 +130,22 @@ class FieldColumns:
     @staticmethod
     def concat(parts):
         """Row-wise concatenation of the results of several calls with the same columns.  Span
-        starts stay relative to each part's own batch."""
+        starts stay relative to each part's own batch; a text column's ``data`` is joined and its
+        ``offsets`` are rebased, so the result is one packed column."""
         import torch
         parts = list(parts)
         cols = []
         for j, c in enumerate(parts[0]):
+            if c.type == TEXT:
+                base, offs = 0, []
+                for p in parts:                         # the sizes are known on the host: no readback
+                    offs.append(p[j].offsets[:-1] + base)
+                    base += int(p[j].data.numel())
+                offs.append(torch.full((1,), base, dtype=torch.int64, device=c.offsets.device))
+                cols.append(Column(c.name, c.field, TEXT, None, torch.cat([p[j].length for p in parts]),
+                                   torch.cat([p[j].status for p in parts]), torch.cat([p[j].data for p in parts]),
+                                   torch.cat(offs)))
+                continue
             ts = [torch.cat([p[j]._tensors()[i] for p in parts]) for i in range(len(c._tensors()))]
             if c.type == SPAN:
                 cols.append(Column(c.name, c.field, c.type, ts[0], ts[1], ts[2]))
@@ -137,15 +173,25 @@ def _column_list(columns):
 
 def _alloc(type_, n, device):
     import torch
-    dt = {SPAN: torch.int64, INT64: torch.int64, INT32: torch.int32, FLOAT64: torch.float64,
+    dt = {SPAN: torch.int64, TEXT: torch.int64, INT64: torch.int64, INT32: torch.int32, FLOAT64: torch.float64,
           FLOAT32: torch.float32}[type_]
     values = torch.empty(n, dtype=dt, device=device)
-    length = torch.empty(n, dtype=torch.int32, device=device) if type_ == SPAN else None
+    length = torch.empty(n, dtype=torch.int32, device=device) if type_ in (SPAN, TEXT) else None
     return values, length, torch.empty(n, dtype=torch.uint8, device=device)
 
 
+def _queue(dev):
+    """(device number or -1 for the host, torch's current stream on it) for a native call."""
+    import torch
+    if dev.type == "cuda":
+        return dev.index if dev.index is not None else torch.cuda.current_device(), \
+            int(torch.cuda.current_stream(dev).cuda_stream)
+    return -1, 0
+
+
 def _launch(data, off, ln, specs, sep, quote, term):
-    """One native call for up to 32 columns; returns the Column objects."""
+    """One native call for up to 32 columns; returns the Column objects.  A text column is located
+    as a span here; :func:`_fill_text` extracts it."""
     import torch
     from ..ops.native import lib, native_errors
     n = int(ln.numel())
@@ -154,12 +200,9 @@ def _launch(data, off, ln, specs, sep, quote, term):
     for name, k, t in specs:
         values, length, status = _alloc(t, n, dev)
         cols.append(Column(name, k, t, values, length, status))
-        raw.append((k, t, values.data_ptr(), length.data_ptr() if length is not None else 0, status.data_ptr()))
-    if dev.type == "cuda":
-        device, stream = dev.index if dev.index is not None else torch.cuda.current_device(), \
-            int(torch.cuda.current_stream(dev).cuda_stream)
-    else:
-        device, stream = -1, 0
+        raw.append((k, SPAN if t == TEXT else t, values.data_ptr(), length.data_ptr() if length is not None else 0,
+                    status.data_ptr()))
+    device, stream = _queue(dev)
     with native_errors():
         lib().field_parse_raw(data.data_ptr(), data.numel(), off.data_ptr(), ln.data_ptr(), ln.dtype == torch.int64, n,
                               device, raw, sep, quote, term, stream)
@@ -178,20 +221,96 @@ def _resolve(data, off, ln, cols, sep, quote, term):
     for i in range(0, len(todo), _MAX_COLS):
         group = todo[i:i + _MAX_COLS]
         spans = _launch(data, off, ln, [(None, c.field, SPAN) for c in group], sep, quote, term)
-        flat = data.view(-1)
         for c, s in zip(group, spans):
             rows = torch.nonzero(c.status == 3).view(-1)
-            st, le = s.start[rows], s.length[rows].to(torch.int64)
-            ends = torch.cumsum(le, 0)
-            pos = torch.repeat_interleave(st - (ends - le), le) + torch.arange(int(ends[-1]), device=flat.device)
-            text = flat[pos].cpu().numpy().tobytes()
-            cuts = np.concatenate([[0], ends.cpu().numpy()])
+            got = extract_text(data, s.start[rows], s.length[rows])
+            text, cuts = got.data.cpu().numpy().tobytes(), got.offsets.cpu().numpy()
             vals = np.array([float(text[cuts[j]:cuts[j + 1]]) for j in range(len(cuts) - 1)], dtype=np.float64)
             if c.type == FLOAT32:
                 with np.errstate(over="ignore"):
                     vals = vals.astype(np.float32)
             c.values[rows] = torch.from_numpy(vals).to(c.values.device)
             c.status[rows] = 0
+
+
+def _text_passes(flat, spans, quote):
+    """measure, cumsum, one readback of all totals, emit: [(data, offsets, lengths)] for the spans
+    [(start int64, length int32, status uint8 or None)] into the flat uint8 ``flat``."""
+    import torch
+    from ..ops.native import lib, native_errors
+    dev = flat.device
+    device, stream = _queue(dev)
+    measured = []
+    with native_errors():
+        for start, length, status in spans:
+            n = int(start.numel())
+            out_len = torch.empty(n, dtype=torch.int32, device=dev)
+            offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            lib().text_measure_raw(flat.data_ptr(), flat.numel(), start.data_ptr(), length.data_ptr(),
+                                   status.data_ptr() if status is not None else 0, n, device, quote, out_len.data_ptr(),
+                                   stream)
+            if n:
+                torch.cumsum(out_len, 0, dtype=torch.int64, out=offsets[1:])
+            measured.append((out_len, offsets))
+        if not measured:
+            return []
+        totals = torch.stack([o[-1] for _, o in measured]).cpu().tolist()
+        out = []
+        for (start, length, status), (out_len, offsets), total in zip(spans, measured, totals):
+            packed = torch.empty(int(total), dtype=torch.uint8, device=dev)
+            lib().text_emit_raw(flat.data_ptr(), flat.numel(), start.data_ptr(), length.data_ptr(),
+                                status.data_ptr() if status is not None else 0, int(start.numel()), device, quote,
+                                offsets.data_ptr(), packed.data_ptr(), packed.numel(), stream)
+            out.append((packed, offsets, out_len))
+    return out
+
+
+def extract_text(data, start, length, status=None, quote=None) -> RaggedBatch:
+    """The values ``data[start[r]:start[r] + length[r]]`` of a flat uint8 tensor, packed end to end
+    on the device of ``data`` (a GPU or the CPU): ``RaggedBatch(data, offsets, lengths)`` with
+    ``offsets`` of ``len(start) + 1`` entries.  ``start``, ``length`` and ``status`` are what a
+    ``span`` column holds (lengths are int32).
+
+    With ``quote`` every doubled quote becomes one (a run of k quote bytes becomes ceil(k / 2)),
+    which is ``value.replace(quote * 2, quote)``: the reading of well-formed files.  The rule is
+    applied to the content whether or not the field was enclosed in quotes, and a lone quote is
+    kept and is not an error.  ``quote=None`` copies the bytes unchanged.  A value whose status is
+    not 0, or that does not lie inside ``data``, has length 0 and is not read.
+
+    Two launches (measure, emit) around a ``torch.cumsum`` on torch's current stream, and one small
+    readback, the total size, to allocate the output."""
+    import torch
+    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8:
+        raise ValueError("extract_text takes uint8 data")
+    q = -1 if quote is None else _one_byte(quote, "quote")
+    dev = data.device
+    flat = (data if data.is_contiguous() else data.contiguous()).view(-1)
+    start = torch.as_tensor(start).to(device=dev, dtype=torch.int64).contiguous().view(-1)
+    length = torch.as_tensor(length).to(dev).view(-1)
+    if length.dtype != torch.int32:
+        length = length.clamp(-1, 2 ** 31 - 1).to(torch.int32)
+    length = length.contiguous()
+    if length.numel() != start.numel():
+        raise ValueError("start and length differ in size")
+    if status is not None:
+        status = torch.as_tensor(status).to(device=dev, dtype=torch.uint8).contiguous().view(-1)
+        if status.numel() != start.numel():
+            raise ValueError("start and status differ in size")
+    (got,) = _text_passes(flat, [(start, length, status)], q)
+    return RaggedBatch(*got)
+
+
+def _fill_text(data, cols, quote):
+    """The text columns of a call: their spans become packed bytes; one readback for all of them.
+    The status is the span's, except that an empty value is 1 (no value) as in a numeric column."""
+    import torch
+    todo = [c for c in cols if c.type == TEXT]
+    if not todo:
+        return
+    got = _text_passes(data.view(-1), [(c.start, c.length, c.status) for c in todo], quote)
+    for c, (packed, offsets, out_len) in zip(todo, got):
+        c.status = torch.where((c.status == 0) & (out_len == 0), torch.ones_like(c.status), c.status)
+        c.data, c.offsets, c.length, c.start = packed, offsets, out_len, None
 
 
 def parse_fields(batch, columns, sep=",", quote=None, terminator=b"\n", resolve_deferred=True) -> FieldColumns:
@@ -201,7 +320,11 @@ def parse_fields(batch, columns, sep=",", quote=None, terminator=b"\n", resolve_
     ``columns``: a list of ``(field number, type)`` or a dict ``name -> (field number, type)``.
     The work runs on torch's current stream and is not waited for, except that
     ``resolve_deferred=True`` reads one small flag back to learn whether any float was deferred;
-    ``resolve_deferred=False`` leaves such values NaN with status 3."""
+    ``resolve_deferred=False`` leaves such values NaN with status 3, and that the ``"text"``
+    columns of a call (alias ``"bytes"``) read their total sizes back, all in one copy, to allocate
+    their ``data``.  A text column holds what :func:`extract_text` gives for the field's span, with
+    ``quote`` as its quote; its status is the span's, except that an empty value has status 1 as in
+    a numeric column, so ``tolist()`` gives ``None`` for absent and for empty fields."""
     import torch
     data, off, ln = batch
     if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8:
@@ -225,6 +348,7 @@ def parse_fields(batch, columns, sep=",", quote=None, terminator=b"\n", resolve_
         cols += _launch(data, off, ln, specs[i:i + _MAX_COLS], s, q, t)
     if resolve_deferred:
         _resolve(data, off, ln, cols, s, q, t)
+    _fill_text(data, cols, q)
     return FieldColumns(cols)
 
 
@@ -255,7 +379,8 @@ def read_delimited_columns(fs, path: str, columns, sep=",", quote=None, delimite
                            skip_rows: int = 0, batch_size: int = 65536, device=None, device_plan="auto") -> FieldColumns:
     """The requested columns of a whole delimited text file, concatenated over an unshuffled
     :class:`DeviceBatchLoader` of ``batch_size`` rows.  The ``start`` of a span column is an offset
-    into the file here (into the batch's data in :func:`parse_fields`).
+    into the file here (into the batch's data in :func:`parse_fields`); a text column is one packed
+    column for the file.
 
     ``header=True``: the first record is read through the client stream and split by the same rule
     on the host; ``columns`` may then name a field by its header text instead of its number (an
