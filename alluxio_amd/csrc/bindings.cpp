@@ -18,6 +18,7 @@
 #include "delim_index.h"
 #include "field_parse.h"
 #include "text_column.h"
+#include "text_dict.h"
 #include "kernels.h"
 #include "seg_ring.h"
 #include "frame_rpc.h"
@@ -730,6 +731,59 @@ PYBIND11_MODULE(_C, m) {
         py::arg("stream") = 0);
   m.def("text_column_launches", &text_column_launches);
 
+  // ---- text dictionaries (text_dict.cpp) ------------------------------------------------------
+  // First-occurrence codes of unquoted text values against a dictionary whose state (table, entry
+  // hashes, bytes and offsets) the caller owns; the passes are described in text_dict.h.
+  // device < 0: host memory, done on return; otherwise queued on `stream`.
+  m.def("text_dict_probe_raw",
+        [](uint64_t data, uint64_t data_bytes, uint64_t start, uint64_t length, uint64_t status, uint64_t n, int device,
+           uint64_t ent_data, uint64_t ent_bytes, uint64_t ent_off, uint64_t D, uint64_t table, uint64_t capacity,
+           bool insert, uint64_t slot_of, uint64_t hash, uint64_t stream) {
+          py::gil_scoped_release rel;
+          text_dict_probe_raw(data, data_bytes, start, length, status, n, device, ent_data, ent_bytes, ent_off, D, table,
+                              capacity, insert, slot_of, hash, stream);
+        },
+        py::arg("data"), py::arg("data_bytes"), py::arg("start"), py::arg("length"), py::arg("status"), py::arg("n"),
+        py::arg("device"), py::arg("ent_data"), py::arg("ent_bytes"), py::arg("ent_off"), py::arg("D"), py::arg("table"),
+        py::arg("capacity"), py::arg("insert"), py::arg("slot_of"), py::arg("hash"), py::arg("stream") = 0);
+  m.def("text_dict_first_raw",
+        [](uint64_t table, uint64_t capacity, uint64_t slot_of, uint64_t length, uint64_t n, int device, uint64_t first,
+           uint64_t first_len, uint64_t stream) {
+          py::gil_scoped_release rel;
+          text_dict_first_raw(table, capacity, slot_of, length, n, device, first, first_len, stream);
+        },
+        py::arg("table"), py::arg("capacity"), py::arg("slot_of"), py::arg("length"), py::arg("n"), py::arg("device"),
+        py::arg("first"), py::arg("first_len"), py::arg("stream") = 0);
+  m.def("text_dict_codes_raw",
+        [](uint64_t table, uint64_t capacity, uint64_t slot_of, uint64_t rank, uint64_t n, uint64_t D, int device,
+           uint64_t codes, uint64_t stream) {
+          py::gil_scoped_release rel;
+          text_dict_codes_raw(table, capacity, slot_of, rank, n, D, device, codes, stream);
+        },
+        py::arg("table"), py::arg("capacity"), py::arg("slot_of"), py::arg("rank"), py::arg("n"), py::arg("D"),
+        py::arg("device"), py::arg("codes"), py::arg("stream") = 0);
+  m.def("text_dict_commit_raw",
+        [](uint64_t table, uint64_t capacity, uint64_t slot_of, uint64_t hash, uint64_t first, uint64_t rank,
+           uint64_t byte_off, uint64_t n, uint64_t D, uint64_t ent_hash, uint64_t ent_off, uint64_t ent_cap,
+           uint64_t old_bytes, int device, uint64_t stream) {
+          py::gil_scoped_release rel;
+          text_dict_commit_raw(table, capacity, slot_of, hash, first, rank, byte_off, n, D, ent_hash, ent_off, ent_cap,
+                               old_bytes, device, stream);
+        },
+        py::arg("table"), py::arg("capacity"), py::arg("slot_of"), py::arg("hash"), py::arg("first"), py::arg("rank"),
+        py::arg("byte_off"), py::arg("n"), py::arg("D"), py::arg("ent_hash"), py::arg("ent_off"), py::arg("ent_cap"),
+        py::arg("old_bytes"), py::arg("device"), py::arg("stream") = 0);
+  m.def("text_dict_rehash_raw",
+        [](uint64_t ent_hash, uint64_t D, uint64_t table, uint64_t capacity, int device, uint64_t stream) {
+          py::gil_scoped_release rel;
+          text_dict_rehash_raw(ent_hash, D, table, capacity, device, stream);
+        },
+        py::arg("ent_hash"), py::arg("D"), py::arg("table"), py::arg("capacity"), py::arg("device"),
+        py::arg("stream") = 0);
+  m.def("text_dict_launches", &text_dict_launches);
+  m.def("set_text_dict_hash_bits", &set_text_dict_hash_bits, py::arg("bits"));
+  m.def("text_dict_hash_bits", &text_dict_hash_bits);
+
   // ---- native S3 data path (http_blob.cpp) --------------------------------------------------
   py::class_<BlobServer>(m, "BlobServer")
       .def(py::init<const std::string&, const std::string&, int>(), py::arg("root"), py::arg("host") = "127.0.0.1",
@@ -1104,6 +1158,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("field_parse_variant", &field_parse_variant);
   m.def("set_text_column_variant", &set_text_column_variant, py::arg("variant"));
   m.def("text_column_variant", &text_column_variant);
+  m.def("set_text_dict_variant", &set_text_dict_variant, py::arg("variant"));
+  m.def("text_dict_variant", &text_dict_variant);
   m.def("set_page_gather_chunk_variant", &set_page_gather_chunk_variant, py::arg("variant"));
   m.attr("COPY_CHUNK") = kCopyChunk;
 }

@@ -13,6 +13,7 @@
 
 #include "field_parse_host.h"
 #include "text_column_host.h"
+#include "text_dict_host.h"
 
 namespace amdx {
 
@@ -222,6 +223,21 @@ hipError_t launch_text_emit(const TextColumnArgs& a, hipStream_t stream);
 // 0 = one lane per value (a serial byte walk), 1 (default) = sixteen lanes per value over 256-byte steps.
 void set_text_column_variant(int variant);
 int text_column_variant();
+
+// Text dictionaries (text_dict.hip): the passes of text_dict_host.h, one launch each.  probe uses
+// global atomics on the table (compare-and-swap, min) and never waits on another lane or
+// workgroup; the other passes are one lane per row (rehash: per entry) with plain loads and stores.
+// The launchers re-check the scalars (text_dict_scalars_ok, and text_dict_probe_fits for probe) and
+// the pointers and refuse with hipErrorInvalidValue.  n == 0 (rehash: D == 0) launches nothing.
+hipError_t launch_text_dict_probe(const TextDictArgs& a, hipStream_t stream);
+hipError_t launch_text_dict_first(const TextDictArgs& a, hipStream_t stream);
+hipError_t launch_text_dict_codes(const TextDictArgs& a, hipStream_t stream);
+hipError_t launch_text_dict_commit(const TextDictArgs& a, hipStream_t stream);
+hipError_t launch_text_dict_rehash(const TextDictArgs& a, hipStream_t stream);
+// probe: 0 (default) = one lane per value (a serial walk), 1 = sixteen lanes per value (hash and
+// compares in 16-byte vectors, the group's lane 0 issues the atomics).
+void set_text_dict_variant(int variant);
+int text_dict_variant();
 
 // CRC32C (Castagnoli, reflected, init/xorout 0xFFFFFFFF) of `n` equal-length pieces
 // (piece i = base + i*piece_bytes, last may be shorter: total_bytes).  `out` device array.

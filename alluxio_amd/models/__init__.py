@@ -4,5 +4,5 @@ into device batches with one kernel launch per batch; ``fields`` parses batches 
 into typed columns where they lie."""
 from .dataset import (DeviceBatchLoader, FixedRecordDataset, IndexedRecordDataset, RaggedBatch,  # noqa: F401
                       build_delimited_index, read_index, write_index)
-from .fields import (Column, FieldColumns, extract_text, parse_fields, read_delimited_columns,  # noqa: F401
-                     split_row)
+from .fields import (Column, FieldColumns, TextDictionary, extract_text, parse_fields,  # noqa: F401
+                     read_delimited_columns, split_row)
