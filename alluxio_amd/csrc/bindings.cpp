@@ -18,6 +18,7 @@
 #include "delim_index.h"
 #include "field_parse.h"
 #include "text_column.h"
+#include "json_fields.h"
 #include "text_dict.h"
 #include "kernels.h"
 #include "seg_ring.h"
@@ -731,6 +732,56 @@ PYBIND11_MODULE(_C, m) {
         py::arg("stream") = 0);
   m.def("text_column_launches", &text_column_launches);
 
+  // ---- JSON Lines columns (json_fields.cpp) ---------------------------------------------------
+  // names: the requested names end to end; cols: (name offset, name length, type 0 span / 1 int64 /
+  // 2 int32 / 3 float64 / 4 float32 / 5 bool / 6 string, values pointer, span-length pointer or 0,
+  // status pointer).  device < 0: host memory, done on return; otherwise queued on `stream`.
+  m.def("json_fields_raw",
+        [](uint64_t data, uint64_t data_bytes, uint64_t off, uint64_t len, bool len_is_64, uint64_t nrows, int device,
+           uint64_t names, uint64_t names_bytes,
+           const std::vector<std::tuple<uint64_t, uint64_t, uint32_t, uint64_t, uint64_t, uint64_t>>& cols,
+           uint32_t terminator, uint64_t stream) {
+          std::vector<JsonFieldsCol> cs;
+          cs.reserve(cols.size());
+          for (auto& c : cols) {
+            JsonFieldsCol x{};
+            // out-of-range numbers stay out of range for the check in json_fields_raw
+            x.name_off = std::get<0>(c) > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)std::get<0>(c);
+            x.name_len = std::get<1>(c) > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)std::get<1>(c);
+            x.type = std::get<2>(c);
+            x.values = reinterpret_cast<void*>(std::get<3>(c));
+            x.length = reinterpret_cast<int32_t*>(std::get<4>(c));
+            x.status = reinterpret_cast<uint8_t*>(std::get<5>(c));
+            cs.push_back(x);
+          }
+          py::gil_scoped_release rel;
+          json_fields_raw(data, data_bytes, off, len, len_is_64, nrows, device, names, names_bytes, terminator, cs,
+                          stream);
+        },
+        py::arg("data"), py::arg("data_bytes"), py::arg("off"), py::arg("len"), py::arg("len_is_64"), py::arg("nrows"),
+        py::arg("device"), py::arg("names"), py::arg("names_bytes"), py::arg("cols"), py::arg("terminator") = 10,
+        py::arg("stream") = 0);
+  m.def("json_fields_launches", &json_fields_launches);
+  // start (int64), length (int32), status (uint8, or 0: none) are a string column's arrays.
+  // measure writes out_len (int32, n) and out_status (uint8, n); emit takes offsets (int64, n + 1).
+  m.def("json_text_measure_raw",
+        [](uint64_t data, uint64_t data_bytes, uint64_t start, uint64_t length, uint64_t status, uint64_t n, int device,
+           uint64_t out_len, uint64_t out_status, uint64_t stream) {
+          py::gil_scoped_release rel;
+          json_text_measure_raw(data, data_bytes, start, length, status, n, device, out_len, out_status, stream);
+        },
+        py::arg("data"), py::arg("data_bytes"), py::arg("start"), py::arg("length"), py::arg("status"), py::arg("n"),
+        py::arg("device"), py::arg("out_len"), py::arg("out_status"), py::arg("stream") = 0);
+  m.def("json_text_emit_raw",
+        [](uint64_t data, uint64_t data_bytes, uint64_t start, uint64_t length, uint64_t status, uint64_t n, int device,
+           uint64_t offsets, uint64_t out, uint64_t out_bytes, uint64_t stream) {
+          py::gil_scoped_release rel;
+          json_text_emit_raw(data, data_bytes, start, length, status, n, device, offsets, out, out_bytes, stream);
+        },
+        py::arg("data"), py::arg("data_bytes"), py::arg("start"), py::arg("length"), py::arg("status"), py::arg("n"),
+        py::arg("device"), py::arg("offsets"), py::arg("out"), py::arg("out_bytes"), py::arg("stream") = 0);
+  m.def("json_text_launches", &json_text_launches);
+
   // ---- text dictionaries (text_dict.cpp) ------------------------------------------------------
   // First-occurrence codes of unquoted text values against a dictionary whose state (table, entry
   // hashes, bytes and offsets) the caller owns; the passes are described in text_dict.h.
@@ -1158,6 +1209,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("field_parse_variant", &field_parse_variant);
   m.def("set_text_column_variant", &set_text_column_variant, py::arg("variant"));
   m.def("text_column_variant", &text_column_variant);
+  m.def("set_json_fields_variant", &set_json_fields_variant, py::arg("variant"));
+  m.def("json_fields_variant", &json_fields_variant);
+  m.def("set_json_text_variant", &set_json_text_variant, py::arg("variant"));
+  m.def("json_text_variant", &json_text_variant);
   m.def("set_text_dict_variant", &set_text_dict_variant, py::arg("variant"));
   m.def("text_dict_variant", &text_dict_variant);
   m.def("set_page_gather_chunk_variant", &set_page_gather_chunk_variant, py::arg("variant"));

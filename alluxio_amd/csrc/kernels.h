@@ -12,6 +12,8 @@
 #include <cstdint>
 
 #include "field_parse_host.h"
+#include "json_fields_host.h"
+#include "json_text_host.h"
 #include "text_column_host.h"
 #include "text_dict_host.h"
 
@@ -223,6 +225,22 @@ hipError_t launch_text_emit(const TextColumnArgs& a, hipStream_t stream);
 // 0 = one lane per value (a serial byte walk), 1 (default) = sixteen lanes per value over 256-byte steps.
 void set_text_column_variant(int variant);
 int text_column_variant();
+
+// JSON Lines columns (json_fields.hip): the values of requested top-level keys located and typed,
+// and JSON string values unescaped into packed bytes.  JsonFieldsArgs, JsonTextArgs and the rules
+// are in json_fields_host.h and json_text_host.h.  One launch each, no workspace, no atomics; only
+// bytes of rows inside [data, data + data_bytes) and of live values are read; emit never writes
+// outside [offsets[r], offsets[r + 1]) cut to [0, out_bytes).  The launchers re-check the scalars
+// (terminator one byte, 1..32 columns, known types, names of 1..255 bytes inside the name buffer,
+// at most 2^31 rows or values) and the pointers and refuse with hipErrorInvalidValue.
+hipError_t launch_json_fields(const JsonFieldsArgs& a, hipStream_t stream);
+hipError_t launch_json_text_measure(const JsonTextArgs& a, hipStream_t stream);
+hipError_t launch_json_text_emit(const JsonTextArgs& a, hipStream_t stream);
+// 0 = one lane per row or value (a serial byte walk), 1 (default) = sixteen lanes over 256-byte steps.
+void set_json_fields_variant(int variant);
+int json_fields_variant();
+void set_json_text_variant(int variant);
+int json_text_variant();
 
 // Text dictionaries (text_dict.hip): the passes of text_dict_host.h, one launch each.  probe uses
 // global atomics on the table (compare-and-swap, min) and never waits on another lane or

@@ -33,6 +33,7 @@ from .dataset import DeviceBatchLoader, IndexedRecordDataset, RaggedBatch, build
 SPAN, INT64, INT32, FLOAT64, FLOAT32, TEXT, CATEGORY = range(7)
 _TYPES = {"span": SPAN, "int64": INT64, "int32": INT32, "float64": FLOAT64, "float32": FLOAT32, "text": TEXT,
           "category": CATEGORY, "int": INT64, "float": FLOAT64, "str": SPAN, "bytes": TEXT, "dict": CATEGORY}
+BOOL = 7                                                # JSON columns only (json_fields.py)
 _MAX_COLS = 32
 
 
@@ -106,8 +107,8 @@ class Column:
         return [v if s == 0 else None for v, s in zip(vals, st)]
 
     def __repr__(self):
-        kind = [k for k, v in _TYPES.items() if v == self.type][0]
-        return f"Column({self.name!r}, field={self.field}, {kind}, rows={len(self.status)})"
+        kind = "bool" if self.type == BOOL else [k for k, v in _TYPES.items() if v == self.type][0]
+        return f"Column({self.name!r}, field={self.field!r}, {kind}, rows={len(self.status)})"
 
 
 class FieldColumns:
