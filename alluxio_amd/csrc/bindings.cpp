@@ -19,6 +19,7 @@
 #include "field_parse.h"
 #include "text_column.h"
 #include "json_fields.h"
+#include "parquet_decode.h"
 #include "text_dict.h"
 #include "kernels.h"
 #include "seg_ring.h"
@@ -782,6 +783,65 @@ PYBIND11_MODULE(_C, m) {
         py::arg("device"), py::arg("offsets"), py::arg("out"), py::arg("out_bytes"), py::arg("stream") = 0);
   m.def("json_text_launches", &json_text_launches);
 
+  // ---- Parquet pages (parquet_decode.cpp) -----------------------------------------------------
+  // Every array is an address; device < 0: host memory, done on return; otherwise queued on
+  // `stream`.  The tables' columns are those of csrc/parquet_host.h.
+  m.def("parquet_walk_raw",
+        [](uint64_t data, uint64_t data_bytes, uint64_t chunk_off, uint64_t chunk_len, uint64_t nchunks, int device,
+           uint64_t counts, uint64_t errors, uint64_t page_base, uint64_t table, uint64_t table_rows, uint64_t stream) {
+          py::gil_scoped_release rel;
+          parquet_walk_raw(data, data_bytes, chunk_off, chunk_len, nchunks, device, counts, errors, page_base, table,
+                           table_rows, stream);
+        },
+        py::arg("data"), py::arg("data_bytes"), py::arg("chunk_off"), py::arg("chunk_len"), py::arg("nchunks"),
+        py::arg("device"), py::arg("counts"), py::arg("errors"), py::arg("page_base") = 0, py::arg("table") = 0,
+        py::arg("table_rows") = 0, py::arg("stream") = 0);
+  m.def("parquet_lz4_raw",
+        [](uint64_t data, uint64_t data_bytes, uint64_t table, uint64_t npages, uint64_t dst_off, uint64_t out,
+           uint64_t out_bytes, uint64_t chunks, uint64_t expect, uint64_t sizes, int device, uint64_t stream) {
+          py::gil_scoped_release rel;
+          parquet_lz4_raw(data, data_bytes, table, npages, dst_off, out, out_bytes, chunks, expect, sizes, device,
+                          stream);
+        },
+        py::arg("data"), py::arg("data_bytes"), py::arg("table"), py::arg("npages"), py::arg("dst_off"), py::arg("out"),
+        py::arg("out_bytes"), py::arg("chunks"), py::arg("expect"), py::arg("sizes"), py::arg("device"),
+        py::arg("stream") = 0);
+  m.def("parquet_hybrid_raw",
+        [](uint64_t data, uint64_t data_bytes, uint64_t streams, uint64_t nstreams, uint64_t out, uint64_t out_n,
+           uint64_t errors, int device, int mode, uint64_t run_counts, uint64_t run_base, uint64_t runs,
+           uint64_t runs_rows, uint64_t stream) {
+          py::gil_scoped_release rel;
+          parquet_hybrid_raw(data, data_bytes, streams, nstreams, out, out_n, errors, mode, run_counts, run_base, runs,
+                             runs_rows, device, stream);
+        },
+        py::arg("data"), py::arg("data_bytes"), py::arg("streams"), py::arg("nstreams"), py::arg("out"),
+        py::arg("out_n"), py::arg("errors"), py::arg("device"), py::arg("mode") = 0, py::arg("run_counts") = 0,
+        py::arg("run_base") = 0, py::arg("runs") = 0, py::arg("runs_rows") = 0, py::arg("stream") = 0);
+  m.def("parquet_place_raw",
+        [](uint64_t data, uint64_t data_bytes, uint64_t pages, uint64_t npages, uint64_t excl, uint64_t idx,
+           uint64_t idx_n, uint64_t dict, uint64_t dict_size, uint64_t stream_err, uint64_t nstreams, uint32_t width,
+           bool is_bool, uint64_t values, uint64_t status, uint64_t rows, int device, uint64_t stream) {
+          py::gil_scoped_release rel;
+          parquet_place_raw(data, data_bytes, pages, npages, excl, idx, idx_n, dict, dict_size, stream_err, nstreams,
+                            width, is_bool, values, status, rows, device, stream);
+        },
+        py::arg("data"), py::arg("data_bytes"), py::arg("pages"), py::arg("npages"), py::arg("excl"), py::arg("idx"),
+        py::arg("idx_n"), py::arg("dict"), py::arg("dict_size"), py::arg("stream_err"), py::arg("nstreams"),
+        py::arg("width"), py::arg("is_bool"), py::arg("values"), py::arg("status"), py::arg("rows"), py::arg("device"),
+        py::arg("stream") = 0);
+  m.def("parquet_bytes_raw",
+        [](uint64_t data, uint64_t data_bytes, uint64_t pages, uint64_t npages, uint64_t excl, uint64_t rows,
+           uint64_t stream_err, uint64_t nstreams, uint64_t start, uint64_t length, uint64_t status, uint64_t nvalues,
+           int device, uint64_t stream) {
+          py::gil_scoped_release rel;
+          parquet_bytes_raw(data, data_bytes, pages, npages, excl, rows, stream_err, nstreams, start, length, status,
+                            nvalues, device, stream);
+        },
+        py::arg("data"), py::arg("data_bytes"), py::arg("pages"), py::arg("npages"), py::arg("excl"), py::arg("rows"),
+        py::arg("stream_err"), py::arg("nstreams"), py::arg("start"), py::arg("length"), py::arg("status"),
+        py::arg("nvalues"), py::arg("device"), py::arg("stream") = 0);
+  m.def("parquet_decode_launches", &parquet_decode_launches);
+
   // ---- text dictionaries (text_dict.cpp) ------------------------------------------------------
   // First-occurrence codes of unquoted text values against a dictionary whose state (table, entry
   // hashes, bytes and offsets) the caller owns; the passes are described in text_dict.h.
@@ -1213,6 +1273,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("json_fields_variant", &json_fields_variant);
   m.def("set_json_text_variant", &set_json_text_variant, py::arg("variant"));
   m.def("json_text_variant", &json_text_variant);
+  m.def("set_parquet_decode_variant", &set_parquet_decode_variant, py::arg("variant"));
+  m.def("parquet_decode_variant", &parquet_decode_variant);
   m.def("set_text_dict_variant", &set_text_dict_variant, py::arg("variant"));
   m.def("text_dict_variant", &text_dict_variant);
   m.def("set_page_gather_chunk_variant", &set_page_gather_chunk_variant, py::arg("variant"));

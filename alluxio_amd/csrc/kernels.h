@@ -14,6 +14,7 @@
 #include "field_parse_host.h"
 #include "json_fields_host.h"
 #include "json_text_host.h"
+#include "parquet_host.h"
 #include "text_column_host.h"
 #include "text_dict_host.h"
 
@@ -241,6 +242,21 @@ void set_json_fields_variant(int variant);
 int json_fields_variant();
 void set_json_text_variant(int variant);
 int json_text_variant();
+
+// Parquet pages (parquet_decode.hip): the passes of parquet_host.h, one launch each, no workspace,
+// no atomics.  Only bytes inside the windows that the tables name, cut to [data, data + data_bytes),
+// are read, and nothing is written outside the outputs' sizes.  hybrid: mode 0 decodes each stream
+// serially, modes 1 to 3 are the cooperative form (count the runs, fill the run table, one thread
+// per value).  The launchers re-check counts (at most 2^31), the value width and the pointers and
+// refuse with hipErrorInvalidValue.
+hipError_t launch_parquet_walk(const PqWalkArgs& a, hipStream_t stream);
+hipError_t launch_parquet_lz4_plan(const PqLz4Args& a, hipStream_t stream);
+hipError_t launch_parquet_hybrid(const PqStreamArgs& a, int mode, hipStream_t stream);
+hipError_t launch_parquet_place(const PqPlaceArgs& a, hipStream_t stream);
+hipError_t launch_parquet_bytes(const PqBytesArgs& a, hipStream_t stream);
+// Which form callers of the hybrid pass should use: 0 = mode 0, 1 (default) = modes 1 to 3.
+void set_parquet_decode_variant(int variant);
+int parquet_decode_variant();
 
 // Text dictionaries (text_dict.hip): the passes of text_dict_host.h, one launch each.  probe uses
 // global atomics on the table (compare-and-swap, min) and never waits on another lane or

@@ -450,7 +450,9 @@ class MigrateDefinition(PlanDefinition):
 class TransformDefinition(PlanDefinition):
     """Table transformation (reference job/server/.../plan/transform/CompactDefinition.java +
     format/{csv,orc,parquet}: rewrite each partition's files as at most ``file.count.max``
-    Parquet files under the transformation's location)."""
+    Parquet files under the transformation's location).  ``parquet.compression=<name>`` in the
+    definition is passed to the Parquet writer; with ``lz4`` the output is what
+    ``models.read_parquet_columns`` decodes on the device."""
 
     @staticmethod
     def _max_files(defn: str) -> int:
@@ -459,6 +461,14 @@ class TransformDefinition(PlanDefinition):
             if k.strip() == "file.count.max":
                 return max(1, int(v))
         return 100
+
+    @staticmethod
+    def _write_options(defn: str) -> dict:
+        for kv in defn.replace(";", " ").split():
+            k, _, v = kv.partition("=")
+            if k.strip() == "parquet.compression" and v.strip():
+                return {"compression": v.strip()}
+        return {}
 
     def select_executors(self, cfg, job_workers, fs):
         if not job_workers:
@@ -484,7 +494,7 @@ class TransformDefinition(PlanDefinition):
             if part.num_rows == 0 and i > 0:
                 break
             buf = io.BytesIO()
-            pq.write_table(part, buf)
+            pq.write_table(part, buf, **self._write_options(cfg.transform))
             path = posixpath.join(args["dst"], f"part-{i:05d}.parquet")
             if ctx.fs.exists(path):
                 ctx.fs.delete(path)

@@ -706,6 +706,28 @@ class DeviceBatchLoader:
             off, ln = off // item, ln // item
         return RaggedBatch(data.view(self.ds.dtype), off, ln)
 
+    def gather(self, indices) -> RaggedBatch:
+        """The records ``indices`` of an :class:`IndexedRecordDataset` as one :class:`RaggedBatch`, now:
+        what iteration yields for that batch, for callers that choose the records themselves.  The
+        work runs on the loader's stream and torch's current stream waits for it."""
+        import torch
+        if not self.ragged:
+            raise TypeError("gather takes a loader over an IndexedRecordDataset")
+        ix = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        if len(ix) and (int(ix.min()) < 0 or int(ix.max()) >= len(self.ds)):
+            raise IndexError("a record index outside the dataset")
+        if self.stream is None:
+            return self._fill_ragged(ix)
+        with torch.cuda.stream(self.stream):
+            batch = self._fill_ragged(ix)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(ev)
+        for t in batch:
+            t.record_stream(cur)
+        return batch
+
     # ---- iteration ----------------------------------------------------------------------------
     def __len__(self):
         n = len(self.ds)
