@@ -20,6 +20,7 @@
 #include "text_column.h"
 #include "json_fields.h"
 #include "parquet_decode.h"
+#include "parquet_encode.h"
 #include "text_dict.h"
 #include "kernels.h"
 #include "seg_ring.h"
@@ -841,6 +842,39 @@ PYBIND11_MODULE(_C, m) {
         py::arg("stream_err"), py::arg("nstreams"), py::arg("start"), py::arg("length"), py::arg("status"),
         py::arg("nvalues"), py::arg("device"), py::arg("stream") = 0);
   m.def("parquet_decode_launches", &parquet_decode_launches);
+
+  // ---- Parquet page encode (parquet_encode.cpp) -----------------------------------------------
+  // The write side: the page table (csrc/parquet_encode_host.h) holds the addresses of the
+  // columns' arrays and the places in the row-group buffer.
+  m.def("parquet_encode_measure_raw",
+        [](uint64_t pages, uint64_t npages, uint64_t first, uint64_t last, uint64_t largest, uint64_t flags,
+           uint64_t text_bytes, uint64_t flat_n, uint64_t measure, int device, uint64_t stream) {
+          py::gil_scoped_release rel;
+          parquet_encode_measure_raw(pages, npages, first, last, largest, flags, text_bytes, flat_n, measure, device,
+                                     stream);
+        },
+        py::arg("pages"), py::arg("npages"), py::arg("first"), py::arg("last"), py::arg("largest"), py::arg("flags"),
+        py::arg("text_bytes"), py::arg("flat_n"), py::arg("measure"), py::arg("device"), py::arg("stream") = 0);
+  m.def("parquet_encode_emit_raw",
+        [](int pass, uint64_t pages, uint64_t npages, uint64_t first, uint64_t last, uint64_t largest, uint64_t flags,
+           uint64_t rank, uint64_t text_at, uint64_t scratch, uint64_t flat_n, uint64_t out, uint64_t out_bytes,
+           int device, uint64_t stream) {
+          py::gil_scoped_release rel;
+          parquet_encode_emit_raw(pass, pages, npages, first, last, largest, flags, rank, text_at, scratch, flat_n, out,
+                                  out_bytes, device, stream);
+        },
+        py::arg("pass_"), py::arg("pages"), py::arg("npages"), py::arg("first"), py::arg("last"), py::arg("largest"),
+        py::arg("flags"), py::arg("rank"), py::arg("text_at"), py::arg("scratch"), py::arg("flat_n"), py::arg("out"),
+        py::arg("out_bytes"), py::arg("device"), py::arg("stream") = 0);
+  m.def("parquet_encode_copy_raw",
+        [](uint64_t blob, uint64_t blob_bytes, uint64_t segs, uint64_t nsegs, uint64_t out, uint64_t out_bytes,
+           int device, uint64_t stream) {
+          py::gil_scoped_release rel;
+          parquet_encode_copy_raw(blob, blob_bytes, segs, nsegs, out, out_bytes, device, stream);
+        },
+        py::arg("blob"), py::arg("blob_bytes"), py::arg("segs"), py::arg("nsegs"), py::arg("out"), py::arg("out_bytes"),
+        py::arg("device"), py::arg("stream") = 0);
+  m.def("parquet_encode_launches", &parquet_encode_launches);
 
   // ---- text dictionaries (text_dict.cpp) ------------------------------------------------------
   // First-occurrence codes of unquoted text values against a dictionary whose state (table, entry

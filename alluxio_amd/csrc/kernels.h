@@ -14,6 +14,7 @@
 #include "field_parse_host.h"
 #include "json_fields_host.h"
 #include "json_text_host.h"
+#include "parquet_encode_host.h"
 #include "parquet_host.h"
 #include "text_column_host.h"
 #include "text_dict_host.h"
@@ -257,6 +258,12 @@ hipError_t launch_parquet_bytes(const PqBytesArgs& a, hipStream_t stream);
 // Which form callers of the hybrid pass should use: 0 = mode 0, 1 (default) = modes 1 to 3.
 void set_parquet_decode_variant(int variant);
 int parquet_decode_variant();
+
+// Parquet page encode (parquet_encode.hip): pass `pass` (kPePass*) of parquet_encode_host.h over the
+// pages [a.first, a.last), one launch; `largest` is the most rows (pack: value bytes) that a page of
+// the range has and sizes the grid.  Only addresses that the page table names are read, and nothing
+// is written outside the flat arrays, the measure table and [out, out + out_bytes).
+hipError_t launch_parquet_encode(const PeArgs& a, int pass, uint64_t largest, hipStream_t stream);
 
 // Text dictionaries (text_dict.hip): the passes of text_dict_host.h, one launch each.  probe uses
 // global atomics on the table (compare-and-swap, min) and never waits on another lane or

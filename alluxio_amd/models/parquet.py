@@ -28,6 +28,13 @@ INT96 and FIXED_LEN_BYTE_ARRAY, every codec but UNCOMPRESSED and LZ4_RAW (so SNA
 BROTLI and the Hadoop-framed LZ4), BIT_PACKED levels, encrypted files, and the DELTA_* and
 BYTE_STREAM_SPLIT value encodings, which only a page header reveals and which are therefore
 raised after the page walk.  Columns that are not selected may be of any kind.
+
+The write side, :func:`write_parquet_columns` and :class:`ParquetWriter`, turns a
+:class:`FieldColumns` back into a file (``csrc/parquet_encode_host.h`` has the rules): measure (a
+flag per row and the sizes per page, the one readback), rank (``torch.cumsum``), emit (level bits,
+PLAIN values, text, bit-packed booleans and dictionary indices, and the host-built headers, all into
+one buffer per row group), then a footer from a small Thrift compact writer.  Uncompressed, V1 data
+pages, flat columns, no statistics.
 """
 from __future__ import annotations
 
@@ -37,7 +44,7 @@ from collections import namedtuple
 import numpy as np
 
 from .dataset import DeviceBatchLoader, IndexedRecordDataset, RaggedBatch
-from .fields import (BOOL, CATEGORY, FLOAT32, FLOAT64, INT32, INT64, TEXT, Column, FieldColumns,
+from .fields import (BOOL, CATEGORY, FLOAT32, FLOAT64, INT32, INT64, SPAN, TEXT, Column, FieldColumns, TextDictionary,
                      _category_dictionaries, _queue, extract_text)
 
 PHYSICAL = ["BOOLEAN", "INT32", "INT64", "INT96", "FLOAT", "DOUBLE", "BYTE_ARRAY", "FIXED_LEN_BYTE_ARRAY"]
@@ -474,7 +481,10 @@ def _chunk_tables(pages, lf, nrows):
         else:
             ds[k] = (int(r[_T_PAYLOAD]), int(r[_T_COMP]), 1, 0, 1, nv, rb, 0)
         # bool RLE: a 4-byte length, then width 1; indices: a width byte.  No values: nothing is read.
-        vs[k] = (voff, vlen, 1 if src == 2 else 2, skip, 1, nv if src in (1, 2) else 0, rb, 0)
+        if src in (1, 2):
+            vs[k] = (voff, vlen, 1 if src == 2 else 2, skip, 1, nv, rb, 0)
+        else:                                           # PLAIN values are no stream: their first byte is no bit width
+            vs[k] = (0, 0, 0, 0, 1, 0, rb, 0)
         rb += nv
     return pp, ds, vs, dict_pages
 
@@ -745,3 +755,502 @@ def read_parquet_columns(fs, path: str, columns=None, row_groups=None, device=No
     stream.  See the module's documentation for types, statuses and what is refused."""
     parts = list(parquet_row_groups(fs, path, columns, row_groups, device, device_plan, dictionaries))
     return FieldColumns.concat(parts)
+
+
+# ---- writing ------------------------------------------------------------------------------------------
+# page-table and measure columns of csrc/parquet_encode_host.h
+_PE_COLS, _PM_COLS = 16, 8
+(_E_KIND, _E_WIDTH, _E_VALUES, _E_STATUS, _E_OFFSETS, _E_AUX, _E_ROW, _E_ROWS, _E_FLAT, _E_LEVEL, _E_VALOFF, _E_VALBYTES,
+ _E_NVALID) = range(13)
+_M_VALID, _M_BAD, _M_TEXT, _M_MAXCODE, _M_OUTSIDE = range(5)
+_K_FIXED, _K_BOOL, _K_TEXT, _K_INDEX = range(4)
+_PASS_ROWS, _PASS_TEXT, _PASS_PACK = 1, 2, 3
+_KIND_ORDER = {_K_FIXED: 0, _K_BOOL: 1, _K_INDEX: 2, _K_TEXT: 3}      # the table's order: each pass takes a range
+_MAX_BODY = 2 ** 31
+CREATED_BY = "alluxio-amd parquet writer (device page encode)"
+_WRITE_KINDS = {INT64: ("INT64", _K_FIXED, 8), INT32: ("INT32", _K_FIXED, 4), FLOAT64: ("DOUBLE", _K_FIXED, 8),
+                FLOAT32: ("FLOAT", _K_FIXED, 4), BOOL: ("BOOLEAN", _K_BOOL, 1), TEXT: ("BYTE_ARRAY", _K_TEXT, 0),
+                CATEGORY: ("BYTE_ARRAY", _K_INDEX, 0)}
+
+
+def _varint(v: int) -> bytes:
+    out = bytearray()
+    while v >= 0x80:
+        out.append((v & 0x7F) | 0x80)
+        v >>= 7
+    out.append(v)
+    return bytes(out)
+
+
+class _ThriftOut:
+    """A writer of the Thrift compact protocol, the counterpart of :class:`_Thrift`: fields are
+    written in ascending id order inside ``struct`` / ``end``."""
+
+    def __init__(self):
+        self.b = bytearray()
+        self._last = [0]
+
+    def _field(self, fid: int, t: int):
+        d = fid - self._last[-1]
+        if 0 < d <= 15:
+            self.b.append((d << 4) | t)
+        else:
+            self.b.append(t)
+            self.b += _varint((fid << 1) ^ (fid >> 63))
+        self._last[-1] = fid
+
+    def i32(self, fid: int, v: int):
+        self._field(fid, 5)
+        self.b += _varint(((v << 1) ^ (v >> 63)) & 0xFFFFFFFFFFFFFFFF)
+
+    def i64(self, fid: int, v: int):
+        self._field(fid, 6)
+        self.b += _varint(((v << 1) ^ (v >> 63)) & 0xFFFFFFFFFFFFFFFF)
+
+    def binary(self, fid: int, v: bytes):
+        self._field(fid, 8)
+        self.b += _varint(len(v)) + v
+
+    def list_(self, fid: int, etype: int, n: int):
+        self._field(fid, 9)
+        self.b += bytes([(n << 4) | etype]) if n < 15 else bytes([0xF0 | etype]) + _varint(n)
+
+    def struct(self, fid=None):
+        """Opens a struct: a field of the current one, or (``None``) a list element or the top."""
+        if fid is not None:
+            self._field(fid, 12)
+        self._last.append(0)
+
+    def end(self):
+        self.b.append(0)
+        self._last.pop()
+
+
+def _page_header(page_type: int, size: int, num_values: int, encoding: int) -> bytes:
+    t = _ThriftOut()
+    t.struct()
+    t.i32(1, page_type)
+    t.i32(2, size)
+    t.i32(3, size)
+    t.struct(5 if page_type == 0 else 7)
+    t.i32(1, num_values)
+    t.i32(2, encoding)
+    if page_type == 0:
+        t.i32(3, 3)                                     # definition and repetition levels: RLE
+        t.i32(4, 3)
+    t.end()
+    t.end()
+    return bytes(t.b)
+
+
+class _WriteColumn:
+    __slots__ = ("name", "type", "physical", "kind", "width", "values", "status", "offsets", "data_bytes", "dictionary",
+                 "required", "keep")
+
+
+def _write_columns(columns, required):
+    """The columns of a FieldColumns as the writer takes them: contiguous tensors of the expected
+    types on one device.  Raises for what cannot be written."""
+    import torch
+    if not isinstance(columns, FieldColumns):
+        raise TypeError(f"the columns are a FieldColumns, got {type(columns).__name__}")
+    if len(columns) == 0:
+        raise ValueError("at least one column is required")
+    dev = columns[0].status.device
+    want = {INT64: torch.int64, INT32: torch.int32, FLOAT64: torch.float64, FLOAT32: torch.float32, BOOL: torch.bool,
+            CATEGORY: torch.int32}
+    out, rows = [], columns.rows
+    for j, c in enumerate(columns):
+        name = c.name if c.name is not None else f"f{j}"
+        if c.type == SPAN:
+            raise TypeError(f"column {name!r} is a span column: its starts point into a batch that is gone; parse it "
+                            f"as text")
+        if c.type not in _WRITE_KINDS or (c.type == TEXT and c.data is None) or (c.type == CATEGORY and c.values is None):
+            raise TypeError(f"column {name!r} cannot be written: it holds no values of a known type")
+        w = _WriteColumn()
+        w.name, w.type = name, c.type
+        w.physical, w.kind, w.width = _WRITE_KINDS[c.type]
+        w.required = name in required
+        w.dictionary, w.offsets, w.data_bytes = None, None, 0
+        tensors = [c.status] + ([c.data, c.offsets] if c.type == TEXT else [c.values])
+        if any(t.device != dev for t in tensors) or len(c.status) != rows or c.status.dtype != torch.uint8:
+            raise ValueError(f"column {name!r}: all columns have the same rows, on one device")
+        w.status = c.status.contiguous()
+        if c.type == TEXT:
+            if c.data.dtype != torch.uint8 or c.offsets.dtype != torch.int64 or c.offsets.numel() != rows + 1:
+                raise TypeError(f"column {name!r}: a text column has uint8 data and rows + 1 int64 offsets")
+            w.values, w.offsets = c.data.contiguous().view(-1), c.offsets.contiguous()
+            w.data_bytes = int(w.values.numel())
+        else:
+            if c.values.dtype != want[c.type] or c.values.numel() != rows:
+                raise TypeError(f"column {name!r}: the values are {c.values.dtype}, not {want[c.type]}")
+            w.values = c.values.contiguous()
+            if c.type == BOOL:
+                w.values = w.values.view(torch.uint8)
+            if c.type == CATEGORY:
+                if not isinstance(c.dictionary, TextDictionary) or c.dictionary.device != dev:
+                    raise ValueError(f"column {name!r}: a category column has a TextDictionary on the columns' device")
+                w.dictionary = c.dictionary
+        out.append(w)
+    if len({w.name for w in out}) != len(out):
+        raise ValueError(f"the column names are not distinct: {[w.name for w in out]}")
+    unknown = sorted(set(required) - {w.name for w in out})
+    if unknown:
+        raise ValueError(f"required names columns that are not there: {unknown}")
+    return out, dev
+
+
+class _Group:
+    """One row group on its way: the page table, the flat arrays and the measure table."""
+    __slots__ = ("cols", "r0", "rows", "dev", "table", "index", "flags", "text_bytes", "measure", "flat_n", "layout")
+
+
+def _measure_group(cols, r0, r1, page_rows, dev) -> _Group:
+    """The measure pass over rows [r0, r1) of the columns: one launch and the one readback."""
+    import torch
+    from ..ops.native import lib, native_errors
+    g = _Group()
+    g.cols, g.r0, g.rows, g.dev = cols, r0, r1 - r0, dev
+    n = g.rows
+    pr = n if page_rows is None else min(int(page_rows), n)
+    per_col = -(-n // pr)
+    order = sorted(range(len(cols)), key=lambda j: (_KIND_ORDER[cols[j].kind], j))
+    g.table = np.zeros((per_col * len(cols), _PE_COLS), dtype=np.int64)
+    g.index = {}
+    p = 0
+    for j in order:
+        c = cols[j]
+        g.index[j] = list(range(p, p + per_col))
+        for k in range(per_col):
+            row = g.table[p]
+            row[_E_KIND], row[_E_WIDTH] = c.kind, c.width
+            row[_E_VALUES], row[_E_STATUS] = _ptr(c.values), c.status.data_ptr()
+            row[_E_OFFSETS] = c.offsets.data_ptr() if c.offsets is not None else 0
+            row[_E_AUX] = c.data_bytes if c.kind == _K_TEXT else len(c.dictionary) if c.kind == _K_INDEX else 0
+            row[_E_ROW], row[_E_ROWS], row[_E_FLAT] = r0 + k * pr, min(pr, n - k * pr), j * n + k * pr
+            row[_E_LEVEL] = -1
+            p += 1
+    g.flat_n = len(cols) * n
+    g.flags = torch.empty(g.flat_n, dtype=torch.uint8, device=dev)
+    g.text_bytes = torch.empty(g.flat_n, dtype=torch.int32, device=dev) if any(c.kind == _K_TEXT for c in cols) else None
+    measure = torch.zeros(len(g.table), _PM_COLS, dtype=torch.int64, device=dev)
+    measure[:, _M_MAXCODE] = -1
+    device, stream = _queue(dev)
+    d_table = _dev_i64(g.table, dev)
+    with native_errors():
+        lib().parquet_encode_measure_raw(d_table.data_ptr(), len(g.table), 0, len(g.table), pr, g.flags.data_ptr(),
+                                         _ptr(g.text_bytes), g.flat_n, measure.data_ptr(), device, stream)
+    g.measure = measure.cpu().numpy()
+    return g
+
+
+def _layout_group(g: _Group, invalid, dict_offsets) -> None:
+    """The places of everything in the row group's buffer, from the measure table; everything that
+    is refused from it is refused here.  ``g.layout``: the table with the dictionary pages added,
+    the copy segments, the blob, the buffer's size and, per column, what the footer needs."""
+    m, cols = g.measure, g.cols
+    table = g.table.copy()
+    extra, segs, blob, chunks = [], [], bytearray(), []
+    pos = 0
+
+    def put(b: bytes):
+        nonlocal pos
+        if b:
+            segs.append((len(blob), pos, len(b)))
+            blob.extend(b)
+            pos += len(b)
+
+    for j, c in enumerate(cols):
+        ps = g.index[j]
+        bad, outside = int(m[ps, _M_BAD].sum()), int(m[ps, _M_OUTSIDE].sum())
+        if bad and invalid == "error":
+            raise ValueError(f"column {c.name!r} has {bad} rows whose status is above 1 (malformed or deferred values); "
+                             f"resolve them or pass invalid='null'")
+        if outside:
+            raise ValueError(f"column {c.name!r} has {outside} codes outside its dictionary of {len(c.dictionary)} entries")
+        nulls = g.rows - int(m[ps, _M_VALID].sum())
+        if c.required and nulls:
+            raise ValueError(f"column {c.name!r} is required and has {nulls} nulls")
+        start, dict_off, width, enc = pos, None, c.width, 0
+        if c.kind == _K_INDEX:
+            top = int(m[ps, _M_MAXCODE].max())
+            entries, width, enc = top + 1, max(1, top.bit_length() if top > 0 else 1), 8
+            off = dict_offsets(c.dictionary)
+            body = int(off[entries] - off[0]) + 4 * entries
+            if body >= _MAX_BODY:
+                raise ValueError(f"column {c.name!r}: a dictionary page of {body} bytes; a page holds less than 2^31")
+            dict_off = pos
+            put(_page_header(2, body, entries, 0))
+            row = np.zeros(_PE_COLS, dtype=np.int64)
+            row[_E_KIND], row[_E_VALUES], row[_E_OFFSETS] = _K_TEXT, c.dictionary._data.data_ptr(), c.dictionary._off.data_ptr()
+            row[_E_AUX], row[_E_ROWS], row[_E_LEVEL] = c.dictionary._nbytes, entries, -1
+            row[_E_VALOFF], row[_E_VALBYTES] = pos, body
+            extra.append(row)
+            pos += body
+        data_off = pos
+        for p in ps:
+            rows, valid = int(table[p, _E_ROWS]), int(m[p, _M_VALID])
+            lev, lev_bits = b"", 0
+            if not c.required:
+                if valid == rows:
+                    run = _varint(rows << 1) + b"\x01"
+                else:
+                    lev_bits = (rows + 7) // 8
+                    run = _varint((lev_bits << 1) | 1)
+                lev = struct.pack("<I", len(run) + lev_bits) + run
+            pre = b""
+            if c.kind == _K_FIXED:
+                vb = valid * c.width
+            elif c.kind == _K_BOOL:
+                vb = (valid + 7) // 8
+            elif c.kind == _K_TEXT:
+                vb = int(m[p, _M_TEXT])
+            else:
+                groups = (valid + 7) // 8
+                pre = bytes([width]) + (_varint((groups << 1) | 1) if valid else b"")
+                vb = groups * width
+            body = len(lev) + lev_bits + len(pre) + vb
+            if body >= _MAX_BODY:
+                raise ValueError(f"column {c.name!r}: a page of {body} bytes; a page holds less than 2^31 (page_rows=)")
+            put(_page_header(0, body, rows, enc) + lev)
+            table[p, _E_LEVEL] = pos if lev_bits else -1
+            pos += lev_bits
+            put(pre)
+            table[p, _E_WIDTH], table[p, _E_VALOFF], table[p, _E_VALBYTES], table[p, _E_NVALID] = width, pos, vb, valid
+            pos += vb
+        if pos - start >= _MAX_BODY:
+            raise ValueError(f"column {c.name!r}: a chunk of {pos - start} bytes; a chunk holds less than 2^31 "
+                             f"(row_group_rows=)")
+        chunks.append((dict_off, data_off, pos - start, enc))
+    if extra:
+        table = np.concatenate([table, np.stack(extra)])
+    g.layout = (table, np.array(segs, dtype=np.int64).reshape(-1, 3), bytes(blob), pos, chunks)
+
+
+def _emit_group(g: _Group):
+    """rank and emit: the row group's bytes as one uint8 tensor on the columns' device."""
+    import torch
+    from ..ops.native import lib, native_errors
+    C = lib()
+    dev = g.dev
+    device, stream = _queue(dev)
+    table, segs, blob, out_bytes, _chunks = g.layout
+    ncol = len(g.table)
+    kinds = table[:, _E_KIND]
+    rank = torch.zeros(g.flat_n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(g.flags, 0, dtype=torch.int64, out=rank[1:])
+    text_at = None
+    if g.text_bytes is not None:
+        text_at = torch.zeros(g.flat_n + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(g.text_bytes, 0, dtype=torch.int64, out=text_at[1:])
+    packed = np.nonzero((kinds[:ncol] == _K_BOOL) | (kinds[:ncol] == _K_INDEX))[0]
+    texts = np.nonzero(kinds == _K_TEXT)[0]
+    scratch = torch.empty(g.flat_n, dtype=torch.int32, device=dev) if len(packed) else None
+    out = torch.zeros(out_bytes, dtype=torch.uint8, device=dev)
+    both = _dev_i64(np.concatenate([table.ravel(), segs.ravel()]), dev)
+    d_table, d_segs = both[:table.size], both[table.size:]
+    d_blob = torch.from_numpy(np.frombuffer(blob, dtype=np.uint8).copy()).to(dev)
+    n = len(table)
+
+    def emit(pass_, first, last, largest):
+        C.parquet_encode_emit_raw(pass_, d_table.data_ptr(), n, first, last, largest, g.flags.data_ptr(), rank.data_ptr(),
+                                  _ptr(text_at), _ptr(scratch), g.flat_n, out.data_ptr(), out_bytes, device, stream)
+
+    with native_errors():
+        C.parquet_encode_copy_raw(d_blob.data_ptr(), d_blob.numel(), _ptr(d_segs), len(segs), out.data_ptr(), out_bytes,
+                                  device, stream)
+        emit(_PASS_ROWS, 0, ncol, int(table[:ncol, _E_ROWS].max()))
+        if len(texts):
+            emit(_PASS_TEXT, int(texts[0]), n, int(table[texts, _E_ROWS].max()))
+        if len(packed):
+            emit(_PASS_PACK, int(packed[0]), int(packed[-1]) + 1, int(table[packed, _E_VALBYTES].max()))
+    return out
+
+
+class ParquetWriter:
+    """Writes :class:`FieldColumns` into one Parquet file, a row group per :meth:`write` call (or
+    several, with ``row_group_rows``), encoded where the columns lie: device tensors by the kernels
+    of ``csrc/parquet_encode.hip``, CPU tensors by host loops that follow the same rules and give the
+    same bytes.  The schema is that of the first call; the footer is written by :meth:`close`, after
+    which :attr:`metadata` holds what :func:`parquet_metadata` would read.  See
+    :func:`write_parquet_columns` for the format."""
+
+    def __init__(self, fs, path: str, required=(), page_rows=None, invalid="error", write_type=None):
+        if invalid not in ("error", "null"):
+            raise ValueError("invalid is 'error' or 'null'")
+        if page_rows is not None and int(page_rows) < 1:
+            raise ValueError("page_rows is at least 1")
+        self.fs, self.path = fs, path
+        self.required = (required,) if isinstance(required, str) else tuple(required)
+        self.page_rows, self.invalid, self.write_type = page_rows, invalid, write_type
+        self.metadata = None
+        self._schema, self._cols, self._f, self._groups, self._rows, self._closed = None, None, None, [], 0, False
+        self._offsets = {}
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, *_):
+        if exc_type is None:
+            self.close()
+        else:
+            self.abort()
+
+    def _dict_offsets(self, d):
+        """The dictionary's offsets on the host, read again only when it has grown."""
+        got = self._offsets.get(id(d))
+        if got is None or len(got[1]) != len(d) + 1:
+            got = (d, d._off[:len(d) + 1].cpu().numpy())
+            self._offsets[id(d)] = got
+        return got[1]
+
+    def _open(self):
+        if self._f is None:
+            self._f = self.fs.create_file(self.path, write_type=self.write_type)
+            self._f.write(b"PAR1")
+
+    def write(self, columns, row_group_rows=None) -> None:
+        """Appends the rows of ``columns`` as one row group (``row_group_rows``: as row groups of
+        that many rows).  Everything that is refused is refused before a byte of the call is
+        written; a call without rows adds no row group."""
+        import torch
+        if self._closed:
+            raise ValueError("the writer is closed")
+        if row_group_rows is not None and int(row_group_rows) < 1:
+            raise ValueError("row_group_rows is at least 1")
+        cols, dev = _write_columns(columns, self.required)
+        schema = [(c.name, c.type) for c in cols]
+        if self._schema is not None and schema != self._schema:
+            raise ValueError(f"the columns differ from those of the first call: {schema} against {self._schema}")
+        rows = columns.rows
+        step = rows if row_group_rows is None else int(row_group_rows)
+        groups = []
+        for r0 in range(0, rows, max(step, 1)):
+            g = _measure_group(cols, r0, min(rows, r0 + step), self.page_rows, dev)
+            _layout_group(g, self.invalid, self._dict_offsets)
+            groups.append(g)
+        self._schema, self._cols = schema, [(c.name, c.physical, c.kind, c.required) for c in cols]
+        self._open()
+        for g in groups:
+            out = _emit_group(g)
+            if dev.type == "cuda":
+                torch.cuda.current_stream(dev).synchronize()
+            base = self._f.tell()
+            self._f.write(out)
+            self._groups.append((g.rows, base, int(out.numel()), g.layout[4]))
+            self._rows += g.rows
+
+    def _footer(self) -> bytes:
+        t = _ThriftOut()
+        t.struct()
+        t.i32(1, 2)
+        t.list_(2, 12, len(self._cols) + 1)
+        t.struct()
+        t.binary(4, b"schema")
+        t.i32(5, len(self._cols))
+        t.end()
+        for name, physical, _kind, required in self._cols:
+            t.struct()
+            t.i32(1, PHYSICAL.index(physical))
+            t.i32(3, 0 if required else 1)
+            t.binary(4, name.encode())
+            if physical == "BYTE_ARRAY":
+                t.i32(6, 0)                             # UTF8
+                t.struct(10)                            # LogicalType: STRING
+                t.struct(1)
+                t.end()
+                t.end()
+            t.end()
+        t.i64(3, self._rows)
+        t.list_(4, 12, len(self._groups))
+        for rows, base, size, chunks in self._groups:
+            t.struct()
+            t.list_(1, 12, len(chunks))
+            for (name, physical, kind, required), (dict_off, data_off, total, enc) in zip(self._cols, chunks):
+                t.struct()
+                t.i64(2, base + (data_off if dict_off is None else dict_off))
+                t.struct(3)
+                t.i32(1, PHYSICAL.index(physical))
+                encs = sorted({0, enc} | (set() if required else {3}))
+                t.list_(2, 5, len(encs))
+                for e in encs:
+                    t.b += _varint(e << 1)
+                t.list_(3, 8, 1)
+                t.b += _varint(len(name.encode())) + name.encode()
+                t.i32(4, 0)
+                t.i64(5, rows)
+                t.i64(6, total)
+                t.i64(7, total)
+                t.i64(9, base + data_off)
+                if dict_off is not None:
+                    t.i64(11, base + dict_off)
+                t.end()
+                t.end()
+            t.i64(2, size)
+            t.i64(3, rows)
+            t.i64(5, base)
+            t.i64(6, size)
+            t.end()
+        t.binary(6, CREATED_BY.encode())
+        t.end()
+        return bytes(t.b)
+
+    def close(self) -> None:
+        """Writes the footer and completes the file.  A writer that was given no columns has no
+        schema and writes nothing."""
+        if self._closed:
+            return
+        self._closed = True
+        if self._schema is None:
+            return
+        self._open()
+        footer = self._footer()
+        self._f.write(footer + struct.pack("<I", len(footer)) + b"PAR1")
+        self._f.close()
+        leaves = [ParquetLeaf(name, physical, "REQUIRED" if required else "OPTIONAL", 0 if required else 1, 0, None)
+                  for name, physical, _kind, required in self._cols]
+        groups = [ParquetRowGroup(rows, [ParquetChunk(name, physical, "UNCOMPRESSED", rows,
+                                                      None if d is None else base + d, base + o, total)
+                                         for (name, physical, _k, _r), (d, o, total, _e) in zip(self._cols, chunks)])
+                  for rows, base, _size, chunks in self._groups]
+        self.metadata = ParquetMetadata(self._rows, leaves, groups, CREATED_BY)
+
+    def abort(self) -> None:
+        """Gives the file up: what was written is dropped and the path does not exist."""
+        self._closed = True
+        if self._f is not None:
+            self._f.cancel()
+            self._f = None
+
+
+def write_parquet_columns(fs, path: str, columns, row_group_rows=None, page_rows=None, required=(), invalid="error",
+                          write_type=None) -> ParquetMetadata:
+    """Writes ``columns`` (a :class:`FieldColumns` on a GPU or on the CPU) as the Parquet file
+    ``path`` and returns its metadata.  The pages are encoded where the columns lie and each row
+    group's bytes go to the output stream as one tensor on that device.
+
+    ``row_group_rows`` cuts the rows into row groups (``None``: one), ``page_rows`` a chunk into data
+    pages (``None``: one).  ``int64`` / ``int32`` / ``float64`` / ``float32`` columns become PLAIN
+    INT64 / INT32 / DOUBLE / FLOAT, ``bool`` PLAIN BOOLEAN, ``text`` PLAIN BYTE_ARRAY (STRING) and
+    ``category`` dictionary-coded BYTE_ARRAY (STRING): per chunk a PLAIN dictionary page with the
+    dictionary's entries up to the largest code that the row group uses, and RLE_DICTIONARY data
+    pages of one bit-packed run.  Columns are OPTIONAL (status 1 is a null; definition levels are one
+    RLE run for a page without nulls, else one bit-packed run) unless named in ``required``.  Data
+    pages are V1, nothing is compressed and no statistics are written.
+
+    Refused before the file is created: a ``span`` column (``TypeError``); a status above 1, a
+    deferred float included, unless ``invalid="null"`` writes such rows as nulls; a null in a
+    required column; a live code outside its dictionary; a page or chunk of 2^31 bytes or more (all
+    ``ValueError``).
+
+    Per row group: one measure launch and one small readback (the sizes of the pages, which the
+    host needs for the page headers), two ``torch.cumsum`` and up to four emit launches, however many
+    columns there are; a category column's dictionary offsets are read once more when it has grown."""
+    w = ParquetWriter(fs, path, required=required, page_rows=page_rows, invalid=invalid, write_type=write_type)
+    try:
+        w.write(columns, row_group_rows)
+        w.close()
+    except BaseException:
+        w.abort()
+        raise
+    return w.metadata

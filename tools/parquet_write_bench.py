@@ -1,0 +1,179 @@
+"""Parquet pages encoded on the GPU: what ``write_parquet_columns`` costs per row group, against
+the copy kernel moving the same bytes, and end to end into the cache against ``pyarrow`` on the host.
+
+The shapes are those of ``tools/parquet_bench.py``, each one row group of 65,536 rows: ``numeric``
+(eight numeric columns) and one string column of 1,000 distinct 12-byte values, as ``text`` and as
+``category``.  The columns are made by ``read_parquet_columns`` from a file that pyarrow wrote from
+a seed, so they lie on the device as a training loop has them.  From one process:
+
+(a) encode: measure (with its readback), layout (the host: sizes, page headers) and emit (the scans,
+    the uploads and the emit launches), everything the caller waits for before the bytes can go to
+    the output stream.  Device events around the whole, ending in a synchronise, and the host clock
+    around each pass with a synchronise after it for the breakdown.
+(b) the roof: the batched copy kernel moving as many bytes as the row group has, in the same rounds,
+    and the encode time as a multiple of it.
+(c) end to end into the cache: ``write_parquet_columns`` against copying every column to the host,
+    ``pa.table``, ``pq.write_table(compression="none")`` and ``fs.write_file``, alternating, by the
+    host clock (both end with the file complete in the cache).
+
+Before timing, the written file is compared with the source through ``pq.read_table``.  One JSON
+line per measurement goes to stdout and to ``--out``.  Needs a GPU: it fails without one."""
+import argparse
+import io
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from parquet_bench import cluster, emit, numeric_table, spread, string_table  # noqa: E402
+
+
+def host_table(pa, cols, cats=()):
+    """The columns copied to the host as a pyarrow table (what a user does without the writer)."""
+    out = {}
+    for c in cols:
+        mask = c.status.cpu().numpy() != 0
+        if c.name in cats:
+            words = pa.array([w.decode() for w in c.dictionary.tolist()], pa.string())
+            codes = pa.array(c.values.cpu().numpy(), pa.int32(), mask=mask)
+            out[c.name] = pa.DictionaryArray.from_arrays(codes, words).cast(pa.string())
+        elif c.data is not None:
+            valid = pa.py_buffer(np.packbits(~mask, bitorder="little"))
+            out[c.name] = pa.StringArray.from_buffers(len(mask), pa.py_buffer(c.offsets.cpu().numpy().astype(np.int32)),
+                                                      pa.py_buffer(c.data.cpu().numpy()), valid, int(mask.sum()))
+        else:
+            out[c.name] = pa.array(c.values.cpu().numpy(), mask=mask)
+    return pa.table(out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=65536)
+    ap.add_argument("--rounds", type=int, default=15)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
+                    help="cpu: a DRAM-tier cluster, the host loops and the host clock (a dry run of the tool)")
+    a = ap.parse_args()
+    import pyarrow as pa
+    import pyarrow.parquet as pq
+    import torch
+
+    from alluxio_amd.models import parquet as P
+    from alluxio_amd.models import read_parquet_columns, write_parquet_columns
+    from alluxio_amd.ops.native import lib
+    gpu = a.device == "cuda"
+    if gpu and not torch.cuda.is_available():
+        raise SystemExit("parquet_write_bench needs a GPU")
+    C = lib()
+    sync = torch.cuda.synchronize if gpu else (lambda: None)
+
+    class Clock:                                        # device events on the GPU, the host clock in a dry run
+        def __init__(self):
+            self.e = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if gpu else None
+
+        def start(self):
+            sync()
+            if gpu:
+                self.e[0].record()
+            self.t = time.perf_counter()
+
+        def stop(self):
+            if gpu:
+                self.e[1].record()
+                self.e[1].synchronize()
+                return self.e[0].elapsed_time(self.e[1])
+            return 1e3 * (time.perf_counter() - self.t)
+
+    shapes = {"numeric": (numeric_table(pa, a.rows, 1), None, ()),
+              "text": (string_table(pa, a.rows, 2), {"s": ("s", "text")}, ()),
+              "category": (string_table(pa, a.rows, 2), {"s": ("s", "category")}, ("s",))}
+    with cluster("2GB", a.device) as c:
+        fs = c.client()
+        for shape, (tbl, spec, cats) in shapes.items():
+            buf = io.BytesIO()
+            pq.write_table(tbl, buf, compression="none", row_group_size=a.rows)
+            fs.write_file(f"/bench/{shape}-src.parquet", buf.getvalue(), write_type="MUST_CACHE")
+            cols = read_parquet_columns(fs, f"/bench/{shape}-src.parquet", spec, device=a.device)
+            write_parquet_columns(fs, f"/bench/{shape}-check.parquet", cols, write_type="MUST_CACHE")
+            got = pq.read_table(io.BytesIO(fs.read_file(f"/bench/{shape}-check.parquet")))
+            if not got.equals(tbl.cast(got.schema)):
+                raise SystemExit(f"{shape}: the written file differs from the source")
+            wcols, dev = P._write_columns(cols, ())
+            writer = P.ParquetWriter(fs, "/bench/unused", write_type="MUST_CACHE")
+            launches = C.parquet_encode_launches()
+            g = P._measure_group(wcols, 0, a.rows, None, dev)
+            P._layout_group(g, "error", writer._dict_offsets)
+            out_bytes = int(P._emit_group(g).numel())
+            launches = C.parquet_encode_launches() - launches
+            src = torch.randint(0, 256, (out_bytes,), dtype=torch.uint8, device=a.device)
+            dst = torch.empty_like(src)
+            stream = int(torch.cuda.current_stream().cuda_stream) if gpu else 0
+            clock = Clock()
+            total, passes, roof = [], [], []
+            for r in range(a.warmup + a.rounds):
+                def encode():
+                    clock.start()
+                    t0 = time.perf_counter()
+                    g = P._measure_group(wcols, 0, a.rows, None, dev)
+                    t1 = time.perf_counter()
+                    P._layout_group(g, "error", writer._dict_offsets)
+                    t2 = time.perf_counter()
+                    P._emit_group(g)
+                    ms = clock.stop()
+                    t3 = time.perf_counter()
+                    return ms, {"measure": 1e3 * (t1 - t0), "layout": 1e3 * (t2 - t1), "emit": 1e3 * (t3 - t2)}
+
+                def copy():
+                    clock.start()
+                    if gpu:
+                        C.batched_copy([(src.data_ptr(), dst.data_ptr(), out_bytes)], stream, False)
+                    else:
+                        dst.copy_(src)
+                    return clock.stop()
+
+                first, second = (encode, copy) if r % 2 == 0 else (copy, encode)
+                x, y = first(), second()
+                enc, cp = (x, y) if r % 2 == 0 else (y, x)
+                if r >= a.warmup:
+                    total.append(enc[0])
+                    passes.append(enc[1])
+                    roof.append(cp)
+            rec = {"phase": "encode", "shape": shape, "rows": a.rows, "row_group_bytes": out_bytes, "launches": launches,
+                   "unit": "ms", "encode": spread(total), "copy_kernel": spread(roof, 4),
+                   "encode_over_copy": spread([t / c_ for t, c_ in zip(total, roof)], 1)}
+            for k in ("measure", "layout", "emit"):
+                rec[k] = spread([p[k] for p in passes])
+            emit(rec, a.out)
+
+            def ours():
+                write_parquet_columns(fs, "/bench/e2e-ours.parquet", cols, write_type="MUST_CACHE")
+                fs.delete("/bench/e2e-ours.parquet")
+
+            def host():
+                buf = io.BytesIO()
+                pq.write_table(host_table(pa, cols, cats), buf, compression="none", row_group_size=a.rows)
+                fs.write_file("/bench/e2e-host.parquet", buf.getvalue(), write_type="MUST_CACHE")
+                fs.delete("/bench/e2e-host.parquet")
+
+            t_ours, t_host = [], []
+            for r in range(a.warmup + a.rounds):
+                for fn, acc in ((ours, t_ours), (host, t_host)) if r % 2 == 0 else ((host, t_host), (ours, t_ours)):
+                    sync()
+                    t0 = time.perf_counter()
+                    fn()
+                    sync()
+                    if r >= a.warmup:
+                        acc.append(1e3 * (time.perf_counter() - t0))
+            emit({"phase": "e2e", "shape": shape, "rows": a.rows, "unit": "ms", "device_write": spread(t_ours),
+                  "host_pyarrow_write": spread(t_host), "host_over_device": spread([h / o for h, o in zip(t_host, t_ours)], 2)},
+                 a.out)
+        fs.close()
+
+
+if __name__ == "__main__":
+    main()
