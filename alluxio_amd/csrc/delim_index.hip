@@ -7,14 +7,14 @@
 // never straddles a page.  One wave owns a tile; a lane reads one vector per step and kDiUnroll
 // steps are in flight (4 KiB per wave and iteration).
 //
-// count: a SWAR compare marks the matching bytes of each 32-bit word and a popcount adds them up;
-//        a wave reduction gives tile_count[t].  Only the first vector of the range and the last
+// count: a SWAR compare (lg_match of lane_group.h) marks the matching bytes of each 32-bit word
+//        and a popcount adds them up; a wave reduction gives tile_count[t].  Only the first vector of the range and the last
 //        vector of the last tile can hold bytes outside the range: those two take the masked
 //        16-bit form below.  Lanes past the end of the range load nothing.
 // scan:  one workgroup, exclusive prefix sum of the tile counts in rounds of 4096 tiles with a
 //        carry; tile_base[ntiles] is the total.
-// emit:  the wave re-reads its tile.  Each vector becomes a 16-bit match mask; a step without a
-//        delimiter ends there (one ballot).  Otherwise the counts of the kDiUnroll vectors of a
+// emit:  the wave re-reads its tile.  Each vector becomes a 16-bit match mask (lg_mask16); a step
+//        without a delimiter ends there (one ballot).  Otherwise the counts of the kDiUnroll vectors of a
 //        lane travel through ONE 64-bit wave scan as four 16-bit fields (a field holds at most
 //        64 * 16 = 1024), so a delimiter's slot is tile_base[t] + the delimiters before it in
 //        address order.  No atomics: the output is the same on every run.
@@ -27,14 +27,13 @@
 // parity plus popcount(ballot(vector parity) & lanes below); inside a vector it is a prefix xor
 // of the quote flags (of the 16-bit mask in emit, of the 0x80 byte flags in count).
 #include "kernels.h"
+#include "lane_group.h"
 
 #include <algorithm>
 
 namespace amdx {
 
 namespace {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kDiThreads = 256;          // 4 waves, each with its own tile
 constexpr int kDiWaves = kDiThreads / 64;
@@ -54,21 +53,9 @@ __device__ __forceinline__ u32x4 di_load(const DelimIndexArgs& a, uint64_t va) {
   else return *p;
 }
 
-// 0x80 in every byte of w that equals the delimiter (dw: the delimiter in all four bytes).  Exact:
-// the add never carries from one byte into the next.
-__device__ __forceinline__ uint32_t di_match(uint32_t w, uint32_t dw) {
-  const uint32_t x = w ^ dw;
-  return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
-}
-
-// Bits 7, 15, 23, 31 of z -> bits 0..3.
-__device__ __forceinline__ uint32_t di_pack(uint32_t z) { return (((z >> 7) * 0x00204081u) >> 21) & 0xFu; }
-
-// Bit j is set when byte j of the vector equals the delimiter and lo <= j < hi.
-__device__ __forceinline__ uint32_t di_mask16(u32x4 v, uint32_t dw, uint32_t lo, uint32_t hi) {
-  const uint32_t m = di_pack(di_match(v.x, dw)) | (di_pack(di_match(v.y, dw)) << 4) |
-                     (di_pack(di_match(v.z, dw)) << 8) | (di_pack(di_match(v.w, dw)) << 12);
-  return m & ((1u << hi) - 1u) & ~((1u << lo) - 1u);
+// The bits j of a 16-bit mask with lo <= j < hi: the bytes of a vector that lie in the range.
+__device__ __forceinline__ uint32_t di_range16(uint32_t lo, uint32_t hi) {
+  return ((1u << hi) - 1u) & ~((1u << lo) - 1u);
 }
 
 // Delimiters among the bytes of vector d (at virtual address va) that lie in [vstart, t1).  Only
@@ -78,9 +65,9 @@ __device__ __forceinline__ uint32_t di_count(u32x4 d, uint32_t dw, uint64_t va, 
   if (va < vstart || (va < t1 && t1 - va < 16)) {
     const uint32_t lo = va < vstart ? (uint32_t)(vstart - va) : 0u;
     const uint32_t hi = t1 - va < 16 ? (uint32_t)(t1 - va) : 16u;
-    return __popc(di_mask16(d, dw, lo, hi));
+    return __popc(lg_mask16(d, dw) & di_range16(lo, hi));
   }
-  return __popc(di_match(d.x, dw)) + __popc(di_match(d.y, dw)) + __popc(di_match(d.z, dw)) + __popc(di_match(d.w, dw));
+  return __popc(lg_match(d.x, dw)) + __popc(lg_match(d.y, dw)) + __popc(lg_match(d.z, dw)) + __popc(lg_match(d.w, dw));
 }
 
 struct DiTile {
@@ -203,7 +190,7 @@ __global__ __launch_bounds__(kDiThreads) void delim_emit_kernel(DelimIndexArgs a
         const uint64_t va = vb + ((uint64_t)u * 64 + lane) * 16;
         const uint32_t lo = va < a.vstart ? (uint32_t)(a.vstart - va) : 0u;
         const uint32_t hi = va >= tl.t1 ? 0u : (tl.t1 - va < 16 ? (uint32_t)(tl.t1 - va) : 16u);
-        m[u] = di_mask16(d[u], dw, lo, hi);
+        m[u] = lg_mask16(d[u], dw) & di_range16(lo, hi);
         p |= (uint64_t)__popc(m[u]) << (16 * u);
       }
       if (__ballot(p != 0) == 0ull) continue;       // wave-uniform
@@ -238,17 +225,6 @@ __device__ __forceinline__ uint32_t di_neither(uint32_t d, uint32_t q) {
   return (d != 0 && q != 0) ? 0u : ((d != 1 && q != 1) ? 1u : 2u);
 }
 
-// Bit j is set when an odd number of the bits below j is set in the 16-bit mask qm: byte j of the
-// vector lies inside quotes when the vector starts outside.
-__device__ __forceinline__ uint32_t di_inside16(uint32_t qm) {
-  uint32_t m = qm;
-  m ^= m << 1;
-  m ^= m << 2;
-  m ^= m << 4;
-  m ^= m << 8;
-  return (m << 1) & 0xFFFFu;
-}
-
 // The masks of one vector: dm = delimiters, qm = quotes, both limited to the bytes of the range.
 struct DiMasks {
   uint32_t dm, qm;
@@ -258,8 +234,8 @@ __device__ __forceinline__ DiMasks di_masks(u32x4 v, uint32_t dw, uint32_t qw, u
   const uint32_t lo = va < vstart ? (uint32_t)(vstart - va) : 0u;
   const uint32_t hi = va >= t1 ? 0u : (t1 - va < 16 ? (uint32_t)(t1 - va) : 16u);
   DiMasks r;
-  r.dm = di_mask16(v, dw, lo, hi);
-  r.qm = di_mask16(v, qw, lo, hi);
+  r.dm = lg_mask16(v, dw) & di_range16(lo, hi);
+  r.qm = lg_mask16(v, qw) & di_range16(lo, hi);
   return r;
 }
 
@@ -271,13 +247,13 @@ __device__ __forceinline__ uint32_t di_quoted_part(const DiMasks& k, uint32_t la
   const uint64_t b = __ballot(__popc(k.qm) & 1);
   const uint32_t before = (*par ^ (uint32_t)__popcll(b & ((1ull << lane) - 1ull))) & 1u;
   *par = (*par ^ (uint32_t)__popcll(b)) & 1u;
-  const uint32_t inq = di_inside16(k.qm) ^ (before ? 0xFFFFu : 0u);
+  const uint32_t inq = lg_inside16(k.qm) ^ (before ? 0xFFFFu : 0u);
   return k.dm & inq;
 }
 
 // What the count kernel needs of one vector, relative to a vector that starts outside quotes:
 // all = its delimiters, odd = those of them inside quotes, par = the parity of its quote bytes.
-// The bytes stay where they are: di_match leaves 0x80 per matching byte, and as the lowest address
+// The bytes stay where they are: lg_match leaves 0x80 per matching byte, and as the lowest address
 // is the lowest byte of a word, p ^= p << 8; p ^= p << 16 turns the quote flags into the parity of
 // the quotes up to and including each byte, p << 8 into that of the quotes before it, and bit 31
 // of p carries on into the next word (m: all ones when the word starts inside).  No 16-bit mask
@@ -290,7 +266,7 @@ __device__ __forceinline__ DiRel di_rel(u32x4 v, uint32_t dw, uint32_t qw, uint6
   if (va < vstart || (va < t1 && t1 - va < 16)) {
     const DiMasks k = di_masks(v, dw, qw, va, vstart, t1);
     r.all = __popc(k.dm);
-    r.odd = __popc(k.dm & di_inside16(k.qm));
+    r.odd = __popc(k.dm & lg_inside16(k.qm));
     r.par = __popc(k.qm) & 1u;
     return r;
   }
@@ -300,8 +276,8 @@ __device__ __forceinline__ DiRel di_rel(u32x4 v, uint32_t dw, uint32_t qw, uint6
   r.odd = 0;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const uint32_t dz = di_match(w[i], dw);
-    uint32_t p = di_match(w[i], qw);
+    const uint32_t dz = lg_match(w[i], dw);
+    uint32_t p = lg_match(w[i], qw);
     p ^= p << 8;
     p ^= p << 16;
     r.all += __popc(dz);
@@ -341,7 +317,7 @@ __global__ __launch_bounds__(kDiThreads) void delim_count_quoted_kernel(DelimInd
         uint32_t any = 0;
 #pragma unroll
         for (int u = 0; u < kDiUnroll; ++u)
-          any |= di_match(d[u].x, qw) | di_match(d[u].y, qw) | di_match(d[u].z, qw) | di_match(d[u].w, qw);
+          any |= lg_match(d[u].x, qw) | lg_match(d[u].y, qw) | lg_match(d[u].z, qw) | lg_match(d[u].w, qw);
         if (__ballot(any != 0) == 0ull) {           // wave-uniform
           uint32_t c = 0;
 #pragma unroll

@@ -5,14 +5,16 @@
 // Variant 0, one lane per row or per value: jf_row / jt_measure_one / jt_emit_one as they stand.
 //
 // Variant 1, cooperative: a group of 16 lanes owns a row or a value (four per wave) and walks it
-// in steps of 256 bytes, lane l of the group loading the 16 bytes at step * 256 + 16 * l.
+// in steps of 256 bytes, lane l of the group loading the 16 bytes at step * 256 + 16 * l.  The
+// loads, masks, scans, the hand-off of state and the placing of kept bytes are the lg_ functions of
+// lane_group.h.
 //
 // Both passes first find the code bytes of escapes.  A vector's backslash mask goes through
 // jf_escaped16; what it needs from the bytes before it is whether the byte before the vector
 // starts an escape.  A vector that is not all backslashes knows what it hands on without knowing
 // what it got, and one of 16 backslashes hands on what it got, so a lane's incoming state is that
 // of the nearest lower lane whose vector is not all backslashes, or the group's carried state:
-// two ballots, no chain through the lanes and no backward walk.
+// two ballots, no chain through the lanes and no backward walk (lg_carry).
 //
 // Locate: the real quotes are the quotes that are no code bytes; their parity below a lane (one
 // ballot) and a prefix xor inside the vector give "inside a string"; a 16-lane signed prefix sum of
@@ -24,8 +26,8 @@
 // values.  Parity, depth, escape state and the member under way are carried from step to step.
 //
 // Unescape: a step whose escapes are all two-byte ones is done in parallel: the starts are
-// dropped, the codes translated, and the kept bytes placed by a 16-lane prefix sum as in
-// text_column.hip; whether the step's last byte starts an escape is carried to the next step.  A
+// dropped, the codes translated, and the kept bytes placed by a 16-lane prefix sum (lg_scan16,
+// lg_place); whether the step's last byte starts an escape is carried to the next step.  A
 // code of no known escape, or a start as the value's last byte, makes the value bad there and
 // then.  A step with a \u escape is walked by lane 0 of the group with jt_span (one dependent byte
 // load per byte: \n is in almost every step of real text, \u is not), which takes an escape that
@@ -37,99 +39,42 @@
 // is assembled from byte loads.  Rows and values are independent, so there are no atomics and no
 // waits between workgroups, and two runs write the same bytes.
 #include "kernels.h"
+#include "lane_group.h"
 
 namespace amdx {
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kJfThreads = 256;
-constexpr int kJfGroup = 16;                        // lanes per row or value in variant 1
-constexpr int kJfPerBlock = kJfThreads / kJfGroup;
-constexpr uint64_t kJfStep = kJfGroup * 16;
-
-__global__ __launch_bounds__(kJfThreads) void json_fields_lane_kernel(JsonFieldsArgs a) {
-  const uint64_t r = (uint64_t)blockIdx.x * kJfThreads + threadIdx.x;
+__global__ __launch_bounds__(kLgThreads) void json_fields_lane_kernel(JsonFieldsArgs a) {
+  const uint64_t r = (uint64_t)blockIdx.x * kLgThreads + threadIdx.x;
   if (r < a.nrows) jf_row(a, r);
 }
 
-__global__ __launch_bounds__(kJfThreads) void json_text_measure_lane_kernel(JsonTextArgs a) {
-  const uint64_t r = (uint64_t)blockIdx.x * kJfThreads + threadIdx.x;
+__global__ __launch_bounds__(kLgThreads) void json_text_measure_lane_kernel(JsonTextArgs a) {
+  const uint64_t r = (uint64_t)blockIdx.x * kLgThreads + threadIdx.x;
   if (r < a.t.n) jt_measure_one(a, r);
 }
 
-__global__ __launch_bounds__(kJfThreads) void json_text_emit_lane_kernel(JsonTextArgs a) {
-  const uint64_t r = (uint64_t)blockIdx.x * kJfThreads + threadIdx.x;
+__global__ __launch_bounds__(kLgThreads) void json_text_emit_lane_kernel(JsonTextArgs a) {
+  const uint64_t r = (uint64_t)blockIdx.x * kLgThreads + threadIdx.x;
   if (r < a.t.n) jt_emit_one(a, r);
 }
 
-// 0x80 in every byte of w that equals the byte replicated in dw (exact: no carry between bytes).
-__device__ __forceinline__ uint32_t jf_match(uint32_t w, uint32_t dw) {
-  const uint32_t x = w ^ dw;
-  return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
-}
-__device__ __forceinline__ uint32_t jf_pack(uint32_t z) { return (((z >> 7) * 0x00204081u) >> 21) & 0xFu; }
-__device__ __forceinline__ uint32_t jf_mask16(u32x4 v, uint32_t dw) {
-  return jf_pack(jf_match(v.x, dw)) | (jf_pack(jf_match(v.y, dw)) << 4) | (jf_pack(jf_match(v.z, dw)) << 8) |
-         (jf_pack(jf_match(v.w, dw)) << 12);
-}
 __device__ __forceinline__ uint32_t jf_byte(uint8_t c) { return (uint32_t)c * 0x01010101u; }
-
-// Bit j: an odd number of the bits below j is set in qm.
-__device__ __forceinline__ uint32_t jf_inside16(uint32_t qm) {
-  uint32_t m = qm;
-  m ^= m << 1;
-  m ^= m << 2;
-  m ^= m << 4;
-  m ^= m << 8;
-  return (m << 1) & 0xFFFFu;
-}
-
-// The 16 bytes at p, or the first rem < 16 of them from byte loads (nothing past the end is read).
-__device__ __forceinline__ u32x4 jf_load(const uint8_t* p, uint64_t rem) {
-  u32x4 v;
-  if (rem >= 16) {
-    __builtin_memcpy(&v, p, 16);                    // any byte phase
-  } else {
-    uint64_t lo = 0, hi = 0;
-    for (uint32_t j = 0; j < (uint32_t)rem; ++j) {
-      const uint64_t b = p[j];
-      if (j < 8) lo |= b << (8 * j);
-      else hi |= b << (8 * (j - 8));
-    }
-    v.x = (uint32_t)lo;
-    v.y = (uint32_t)(lo >> 32);
-    v.z = (uint32_t)hi;
-    v.w = (uint32_t)(hi >> 32);
-  }
-  return v;
-}
-
-__device__ __forceinline__ uint64_t jf_shfl64(uint64_t v, int src) {
-  const uint32_t lo = __shfl((unsigned)v, src), hi = __shfl((unsigned)(v >> 32), src);
-  return ((uint64_t)hi << 32) | lo;
-}
 
 // The code bytes of this lane's vector.  bm: its backslash mask (a vector cut at either end is
 // never all backslashes); *carry: the group's state before the step, replaced by the state after
 // it (uniform in the group).  Every lane of the wave calls it.
 __device__ __forceinline__ uint32_t jf_lane_escaped(uint32_t bm, uint32_t gl, uint32_t g, uint32_t* carry) {
-  const bool all = bm == 0xFFFFu;
   uint32_t mine, unused;
-  jf_escaped16(bm, 0, &mine);                       // exact unless `all`
-  const uint32_t ga = ~(uint32_t)(__ballot(all) >> (g * kJfGroup)) & 0xFFFFu;   // lanes that are not all backslashes
-  const uint32_t gb = (uint32_t)(__ballot(mine != 0) >> (g * kJfGroup)) & 0xFFFFu;
-  const uint32_t below = ga & ((1u << gl) - 1u);
-  const uint32_t in = below ? (gb >> (31 - __builtin_clz(below))) & 1u : *carry;
-  if (ga) *carry = (gb >> (31 - __builtin_clz(ga))) & 1u;
-  return jf_escaped16(bm, in, &unused);
+  jf_escaped16(bm, 0, &mine);                       // exact unless all backslashes
+  return jf_escaped16(bm, lg_carry(bm == 0xFFFFu, mine != 0, gl, g, carry), &unused);
 }
 
-__global__ __launch_bounds__(kJfThreads) void json_fields_coop_kernel(JsonFieldsArgs a) {
-  const uint32_t lane = threadIdx.x & 63, gl = lane & (kJfGroup - 1), g = lane / kJfGroup;
-  const uint32_t gs = g * kJfGroup;
-  const uint64_t r = (uint64_t)blockIdx.x * kJfPerBlock + threadIdx.x / kJfGroup;
+__global__ __launch_bounds__(kLgThreads) void json_fields_coop_kernel(JsonFieldsArgs a) {
+  const uint32_t lane = threadIdx.x & 63, gl = lane & (kLgGroup - 1), g = lane / kLgGroup;
+  const uint32_t gs = g * kLgGroup;                 // the wave lane of the group's lane 0
+  const uint64_t r = (uint64_t)blockIdx.x * kLgPerBlock + threadIdx.x / kLgGroup;
   const bool live = r < a.nrows;
   uint64_t off = 0, n = 0;
   const bool ok = live && jf_row_bytes(a, r, &off, &n);
@@ -137,7 +82,7 @@ __global__ __launch_bounds__(kJfThreads) void json_fields_coop_kernel(JsonFields
   const uint8_t* row = a.data + off;
 
   // the two columns this lane owns: gl and gl + 16; positions are relative to the row
-  const bool own0 = gl < a.ncols, own1 = gl + kJfGroup < a.ncols;
+  const bool own0 = gl < a.ncols, own1 = gl + kLgGroup < a.ncols;
   uint64_t vs0 = kJfNoPos, ve0 = 0, vs1 = kJfNoPos, ve1 = 0;
   bool m0 = false, m1 = false;                      // the member under way has this lane's name as its key
 
@@ -145,42 +90,37 @@ __global__ __launch_bounds__(kJfThreads) void json_fields_coop_kernel(JsonFields
   uint32_t st = kJfBefore, par = 0, depth = 0, ecar = 0;
   uint64_t mstart = 0, colon = kJfNoPos, closed_at = 0;
 
-  for (uint64_t base = 0; __ballot(base < n && st != kJfBadRow) != 0ull; base += kJfStep) {
+  for (uint64_t base = 0; __ballot(base < n && st != kJfBadRow) != 0ull; base += kLgStep) {
     const bool walking = base < n && st != kJfBadRow;
     const uint64_t pos = base + (uint64_t)gl * 16;
     uint32_t bm = 0, qm = 0, om = 0, cm = 0, km = 0, lm = 0, nw = 0;
     if (walking && pos < n) {
       const uint64_t rem = n - pos;
-      const u32x4 v = jf_load(row + pos, rem);
+      const u32x4 v = lg_load16(row + pos, rem);
       const uint32_t valid = rem >= 16 ? 0xFFFFu : ((1u << (uint32_t)rem) - 1u);
       const u32x4 w = {v.x | 0x20202020u, v.y | 0x20202020u, v.z | 0x20202020u, v.w | 0x20202020u};
-      bm = jf_mask16(v, jf_byte('\\')) & valid;
-      qm = jf_mask16(v, jf_byte('"')) & valid;
-      om = jf_mask16(w, jf_byte('{')) & valid;      // { and [ differ in bit 5 only, as do } and ]
-      cm = jf_mask16(w, jf_byte('}')) & valid;
-      km = jf_mask16(v, jf_byte(',')) & valid;
-      lm = jf_mask16(v, jf_byte(':')) & valid;
-      nw = valid & ~(jf_mask16(v, jf_byte(0x20)) | jf_mask16(v, jf_byte(0x09)) | jf_mask16(v, jf_byte(0x0A)) |
-                     jf_mask16(v, jf_byte(0x0D)));
+      bm = lg_mask16(v, jf_byte('\\')) & valid;
+      qm = lg_mask16(v, jf_byte('"')) & valid;
+      om = lg_mask16(w, jf_byte('{')) & valid;      // { and [ differ in bit 5 only, as do } and ]
+      cm = lg_mask16(w, jf_byte('}')) & valid;
+      km = lg_mask16(v, jf_byte(',')) & valid;
+      lm = lg_mask16(v, jf_byte(':')) & valid;
+      nw = valid & ~(lg_mask16(v, jf_byte(0x20)) | lg_mask16(v, jf_byte(0x09)) | lg_mask16(v, jf_byte(0x0A)) |
+                     lg_mask16(v, jf_byte(0x0D)));
     }
     // strings
     const uint32_t rq = qm & ~jf_lane_escaped(bm, gl, g, &ecar);
-    const uint32_t gq = (uint32_t)(__ballot(__popc(rq) & 1) >> gs) & 0xFFFFu;
+    const uint32_t gq = lg_group16(__ballot(__popc(rq) & 1), g);
     const uint32_t before = (par ^ (uint32_t)__popc(gq & ((1u << gl) - 1u))) & 1u;
     par = (par ^ (uint32_t)__popc(gq)) & 1u;
-    const uint32_t outside = ~(jf_inside16(rq) ^ (before ? 0xFFFFu : 0u));
+    const uint32_t outside = ~(lg_inside16(rq) ^ (before ? 0xFFFFu : 0u));
     om &= outside;
     cm &= outside;
     // depth before this lane's vector (wraps as the host's does)
     const uint32_t delta = (uint32_t)__popc(om) - (uint32_t)__popc(cm);
-    uint32_t inc = delta;
-#pragma unroll
-    for (int d = 1; d < kJfGroup; d <<= 1) {
-      const uint32_t o = __shfl_up(inc, d, kJfGroup);
-      if ((int)gl >= d) inc += o;
-    }
-    const uint32_t dl = depth + (inc - delta);
-    depth += __shfl(inc, kJfGroup - 1, kJfGroup);
+    uint32_t dsum;
+    const uint32_t dl = depth + (lg_scan16(delta, gl, &dsum) - delta);
+    depth += dsum;
     // events: commas, colons and closes outside strings with depth 1 before them
     const uint32_t cand = ((km | lm) & outside) | cm;
     uint32_t ev = 0;
@@ -194,8 +134,9 @@ __global__ __launch_bounds__(kJfThreads) void json_fields_coop_kernel(JsonFields
     }
     // nothing but whitespace so far: the first other byte opens the object or the row is bad
     {
-      const uint32_t gn = (uint32_t)(__ballot(nw != 0) >> gs) & 0xFFFFu;
-      const uint64_t first = jf_shfl64(nw ? pos + (uint32_t)__builtin_ctz(nw) : 0, (int)(gs + (gn ? __builtin_ctz(gn) : 0)));
+      const uint32_t gn = lg_group16(__ballot(nw != 0), g);
+      const uint64_t first =
+          lg_shfl64_wave(nw ? pos + (uint32_t)__builtin_ctz(nw) : 0, (int)(gs + (gn ? __builtin_ctz(gn) : 0)));
       if (st == kJfBefore && gn) {
         if (row[first] == '{') {
           st = kJfOpen;
@@ -210,7 +151,7 @@ __global__ __launch_bounds__(kJfThreads) void json_fields_coop_kernel(JsonFields
     for (;;) {
       const uint64_t bal = __ballot(pend != 0 && st == kJfOpen);
       if (bal == 0ull) break;
-      const uint32_t ge = (uint32_t)(bal >> gs) & 0xFFFFu;
+      const uint32_t ge = lg_group16(bal, g);
       const uint32_t src = ge ? (uint32_t)__builtin_ctz(ge) : 0;
       const uint32_t bit = pend ? (uint32_t)__builtin_ctz(pend) : 0;
       const uint32_t kind = ((lm >> bit) & 1u) ? 0u : ((km >> bit) & 1u) ? 1u : 2u;   // colon, comma, close
@@ -222,8 +163,8 @@ __global__ __launch_bounds__(kJfThreads) void json_fields_coop_kernel(JsonFields
         if (colon == kJfNoPos) {
           colon = p;
           m0 = own0 && jf_key_match(row, mstart, p, a.names + a.cols[gl].name_off, a.cols[gl].name_len);
-          m1 = own1 && jf_key_match(row, mstart, p, a.names + a.cols[gl + kJfGroup].name_off,
-                                    a.cols[gl + kJfGroup].name_len);
+          m1 = own1 && jf_key_match(row, mstart, p, a.names + a.cols[gl + kLgGroup].name_off,
+                                    a.cols[gl + kLgGroup].name_len);
         }
         continue;
       }
@@ -251,14 +192,14 @@ __global__ __launch_bounds__(kJfThreads) void json_fields_coop_kernel(JsonFields
       if (pos > closed_at) tail = nw;
       else if (pos + 15 > closed_at) tail = nw & ~((2u << (uint32_t)(closed_at - pos)) - 1u);
     }
-    const uint32_t gt = (uint32_t)(__ballot(tail != 0) >> gs) & 0xFFFFu;
+    const uint32_t gt = lg_group16(__ballot(tail != 0), g);
     if (st == kJfClosed && gt) st = kJfBadRow;
   }
 
   if (!live) return;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const uint32_t col = gl + j * kJfGroup;
+    const uint32_t col = gl + j * kLgGroup;
     if (col >= a.ncols) break;
     const uint64_t vs = j ? vs1 : vs0, ve = j ? ve1 : ve0;
     if (!ok) jf_emit_none(a.cols[col], r, kFpBad);
@@ -269,58 +210,31 @@ __global__ __launch_bounds__(kJfThreads) void json_fields_coop_kernel(JsonFields
   }
 }
 
-// c <= 16 bytes, compact in (lo, hi), to q: at most one store of each size.
-__device__ __forceinline__ void jf_store_pieces(uint8_t* q, uint64_t lo, uint64_t hi, uint32_t c) {
-  if (c & 16) {
-    const u32x4 v = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
-    __builtin_memcpy(q, &v, 16);
-    return;
-  }
-  if (c & 8) {
-    __builtin_memcpy(q, &lo, 8);
-    q += 8;
-    lo = hi;
-  }
-  if (c & 4) {
-    const uint32_t w = (uint32_t)lo;
-    __builtin_memcpy(q, &w, 4);
-    q += 4;
-    lo >>= 32;
-  }
-  if (c & 2) {
-    const uint16_t w = (uint16_t)lo;
-    __builtin_memcpy(q, &w, 2);
-    q += 2;
-    lo >>= 16;
-  }
-  if (c & 1) *q = (uint8_t)lo;
-}
-
 // The walk of one value of n bytes at p by its group.  Returns false for a bad value; *total: the
 // output length.  With EMIT, output byte j in [jlo, jhi) goes to out[lo + j].  Every lane of the
 // wave calls it; a group without a value to walk passes n = 0.
 template <bool EMIT>
 __device__ __forceinline__ bool jt_coop_walk(const uint8_t* p, uint64_t n, uint32_t gl, uint32_t g, uint8_t* out,
                                              int64_t lo, uint64_t jlo, uint64_t jhi, uint64_t* total) {
-  const uint32_t gs = g * kJfGroup;
+  const uint32_t gs = g * kLgGroup;                 // the wave lane of the group's lane 0
   // uniform in the group
   uint64_t done = 0;                                // output bytes before the step
   uint64_t begin = 0;                               // the first byte that is not consumed yet
   uint32_t ecar = 0;                                // the byte before the step starts an escape
   bool bad = false;
-  for (uint64_t base = 0; __ballot(base < n && !bad) != 0ull; base += kJfStep) {
+  for (uint64_t base = 0; __ballot(base < n && !bad) != 0ull; base += kLgStep) {
     const bool walking = base < n && !bad;
     const uint64_t pos = base + (uint64_t)gl * 16;
     uint64_t vlo = 0, vhi = 0;
     uint32_t valid = 0, bm = 0;
     if (walking && pos < n && pos + 16 > begin) {
       const uint64_t rem = n - pos;
-      const u32x4 v = jf_load(p + pos, rem);
+      const u32x4 v = lg_load16(p + pos, rem);
       valid = rem >= 16 ? 0xFFFFu : ((1u << (uint32_t)rem) - 1u);
       if (begin > pos) valid &= ~((1u << (uint32_t)(begin - pos)) - 1u);
-      bm = jf_mask16(v, jf_byte('\\')) & valid;
-      vlo = ((uint64_t)v.y << 32) | v.x;
-      vhi = ((uint64_t)v.w << 32) | v.z;
+      bm = lg_mask16(v, jf_byte('\\')) & valid;
+      vlo = lg_lo64(v);
+      vhi = lg_hi64(v);
     }
     uint32_t keep = valid, c;
     uint64_t j0;                                    // the output index of this lane's first kept byte
@@ -328,8 +242,8 @@ __device__ __forceinline__ bool jt_coop_walk(const uint8_t* p, uint64_t n, uint3
     if (__ballot(walking && (bm != 0 || ecar != 0 || begin > base)) == 0ull) {   // wave-uniform: plain bytes only
       c = (uint32_t)__popc(valid);
       j0 = done + (uint64_t)gl * 16;
-      done += walking ? (n - base < kJfStep ? n - base : kJfStep) : 0;
-      begin = base + kJfStep;
+      done += walking ? (n - base < kLgStep ? n - base : kLgStep) : 0;
+      begin = base + kLgStep;
     } else {
       const uint32_t cin = ecar;                    // the byte before the step starts an escape
       const uint32_t codes = jf_lane_escaped(bm, gl, g, &ecar);
@@ -354,67 +268,41 @@ __device__ __forceinline__ bool jt_coop_walk(const uint8_t* p, uint64_t n, uint3
           vhi = (vhi & ~(0xFFull << sh)) | ((uint64_t)t << sh);
         }
       }
-      const bool group_bad = ((uint32_t)(__ballot(lane_bad) >> gs) & 0xFFFFu) != 0;
-      const bool group_serial = !group_bad && ((uint32_t)(__ballot(lane_u) >> gs) & 0xFFFFu) != 0;
+      const bool group_bad = lg_group16(__ballot(lane_bad), g) != 0;
+      const bool group_serial = !group_bad && lg_group16(__ballot(lane_u), g) != 0;
       keep = valid & ~starts;
       c = (uint32_t)__popc(keep);
-      uint32_t inc = c;
-#pragma unroll
-      for (int d = 1; d < kJfGroup; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d, kJfGroup);
-        if ((int)gl >= d) inc += o;
-      }
-      j0 = done + (inc - c);
-      uint64_t ndone = done + __shfl(inc, kJfGroup - 1, kJfGroup);
-      uint64_t nbegin = base + kJfStep;
+      uint32_t kept;                                // by the group in this step
+      j0 = done + (lg_scan16(c, gl, &kept) - c);
+      uint64_t ndone = done + kept;
+      uint64_t nbegin = base + kLgStep;
       uint32_t sbad = 0;
       if (group_serial && gl == 0) {
         // from the first byte not consumed, or from the backslash before the step whose code
         // opens it (that backslash gave no output); an escape that starts in the step is taken
         // whole, so no escape state is left over
         uint64_t i = begin > base ? begin : base - cin, k = done;
-        const uint64_t stop = n - base < kJfStep ? n : base + kJfStep;
+        const uint64_t stop = n - base < kLgStep ? n : base + kLgStep;
         sbad = jt_span(p, n, &i, stop, &k, EMIT ? out : nullptr, lo, jlo, jhi) ? 0u : 1u;
         ndone = k;
         nbegin = i;
       }
-      done = jf_shfl64(ndone, (int)gs);
-      begin = jf_shfl64(nbegin, (int)gs);
+      done = lg_shfl64_wave(ndone, (int)gs);
+      begin = lg_shfl64_wave(nbegin, (int)gs);
       bad = bad || group_bad || __shfl(sbad, (int)gs) != 0;
       if (group_serial) ecar = 0;
       stored = group_serial || group_bad;
     }
-    if (!EMIT || stored || c == 0 || j0 >= jhi || j0 + c <= jlo) continue;
-    if (keep != 0xFFFFu) {                          // compact the kept bytes
-      uint64_t clo = 0, chi = 0;
-      uint32_t k = 0;
-#pragma unroll
-      for (uint32_t j = 0; j < 16; ++j) {
-        if (!((keep >> j) & 1u)) continue;
-        const uint64_t b = ((j < 8 ? vlo : vhi) >> (8 * (j & 7))) & 0xFFu;
-        if (k < 8) clo |= b << (8 * k);
-        else chi |= b << (8 * (k - 8));
-        ++k;
-      }
-      vlo = clo;
-      vhi = chi;
-    }
-    if (j0 >= jlo && j0 + c <= jhi) {
-      jf_store_pieces(out + (lo + (int64_t)j0), vlo, vhi, c);
-    } else {                                        // the edge of the window: byte by byte, inside it
-      for (uint32_t k = 0; k < c; ++k) {
-        const uint64_t j = j0 + k;
-        if (j >= jlo && j < jhi) out[lo + (int64_t)j] = (uint8_t)((k < 8 ? vlo : vhi) >> (8 * (k & 7)));
-      }
-    }
+    // valid is not always a run of low bits here: only a vector kept whole needs no compaction
+    if (EMIT && !stored) lg_place(out, lo, jlo, jhi, j0, vlo, vhi, keep, c, keep != 0xFFFFu);
   }
   *total = done;
   return !bad;
 }
 
-__global__ __launch_bounds__(kJfThreads) void json_text_measure_coop_kernel(JsonTextArgs a) {
-  const uint32_t lane = threadIdx.x & 63, gl = lane & (kJfGroup - 1), g = lane / kJfGroup;
-  const uint64_t r = (uint64_t)blockIdx.x * kJfPerBlock + threadIdx.x / kJfGroup;
+__global__ __launch_bounds__(kLgThreads) void json_text_measure_coop_kernel(JsonTextArgs a) {
+  const uint32_t lane = threadIdx.x & 63, gl = lane & (kLgGroup - 1), g = lane / kLgGroup;
+  const uint64_t r = (uint64_t)blockIdx.x * kLgPerBlock + threadIdx.x / kLgGroup;
   uint64_t off = 0, n = 0, total = 0;
   const bool ok = r < a.t.n && tc_live(a.t, r, &off, &n);
   if (!ok) n = 0;                                   // such a value is not read
@@ -425,9 +313,9 @@ __global__ __launch_bounds__(kJfThreads) void json_text_measure_coop_kernel(Json
   }
 }
 
-__global__ __launch_bounds__(kJfThreads) void json_text_emit_coop_kernel(JsonTextArgs a) {
-  const uint32_t lane = threadIdx.x & 63, gl = lane & (kJfGroup - 1), g = lane / kJfGroup;
-  const uint64_t r = (uint64_t)blockIdx.x * kJfPerBlock + threadIdx.x / kJfGroup;
+__global__ __launch_bounds__(kLgThreads) void json_text_emit_coop_kernel(JsonTextArgs a) {
+  const uint32_t lane = threadIdx.x & 63, gl = lane & (kLgGroup - 1), g = lane / kLgGroup;
+  const uint64_t r = (uint64_t)blockIdx.x * kLgPerBlock + threadIdx.x / kLgGroup;
   uint64_t off = 0, n = 0, jlo = 0, jhi = 0, total = 0;
   int64_t lo = 0;
   const bool ok = r < a.t.n && tc_live(a.t, r, &off, &n) && tc_window(a.t, r, &lo, &jlo, &jhi);
@@ -444,7 +332,7 @@ int g_jt_variant = 1;
 bool jt_args_ok(const JsonTextArgs& a) { return a.t.n <= (1ull << 31); }
 
 unsigned jf_grid(uint64_t n, int variant) {
-  const uint64_t per = variant == 1 ? kJfPerBlock : kJfThreads;
+  const uint64_t per = variant == 1 ? kLgPerBlock : kLgThreads;
   return (unsigned)((n + per - 1) / per);
 }
 
@@ -460,8 +348,8 @@ hipError_t launch_json_fields(const JsonFieldsArgs& a, hipStream_t stream) {
   if (a.nrows == 0) return hipSuccess;
   if (!a.off || !a.len || !a.names || (!a.data && a.data_bytes)) return hipErrorInvalidValue;
   const dim3 grid(jf_grid(a.nrows, g_jf_variant));
-  if (g_jf_variant == 1) hipLaunchKernelGGL(json_fields_coop_kernel, grid, dim3(kJfThreads), 0, stream, a);
-  else hipLaunchKernelGGL(json_fields_lane_kernel, grid, dim3(kJfThreads), 0, stream, a);
+  if (g_jf_variant == 1) hipLaunchKernelGGL(json_fields_coop_kernel, grid, dim3(kLgThreads), 0, stream, a);
+  else hipLaunchKernelGGL(json_fields_lane_kernel, grid, dim3(kLgThreads), 0, stream, a);
   return hipGetLastError();
 }
 
@@ -471,8 +359,8 @@ hipError_t launch_json_text_measure(const JsonTextArgs& a, hipStream_t stream) {
   if (!a.t.start || !a.t.length || !a.t.out_len || !a.out_status || (!a.t.data && a.t.data_bytes))
     return hipErrorInvalidValue;
   const dim3 grid(jf_grid(a.t.n, g_jt_variant));
-  if (g_jt_variant == 1) hipLaunchKernelGGL(json_text_measure_coop_kernel, grid, dim3(kJfThreads), 0, stream, a);
-  else hipLaunchKernelGGL(json_text_measure_lane_kernel, grid, dim3(kJfThreads), 0, stream, a);
+  if (g_jt_variant == 1) hipLaunchKernelGGL(json_text_measure_coop_kernel, grid, dim3(kLgThreads), 0, stream, a);
+  else hipLaunchKernelGGL(json_text_measure_lane_kernel, grid, dim3(kLgThreads), 0, stream, a);
   return hipGetLastError();
 }
 
@@ -482,8 +370,8 @@ hipError_t launch_json_text_emit(const JsonTextArgs& a, hipStream_t stream) {
   if (!a.t.start || !a.t.length || !a.t.offsets || (!a.t.data && a.t.data_bytes) || (!a.t.out && a.t.out_bytes))
     return hipErrorInvalidValue;
   const dim3 grid(jf_grid(a.t.n, g_jt_variant));
-  if (g_jt_variant == 1) hipLaunchKernelGGL(json_text_emit_coop_kernel, grid, dim3(kJfThreads), 0, stream, a);
-  else hipLaunchKernelGGL(json_text_emit_lane_kernel, grid, dim3(kJfThreads), 0, stream, a);
+  if (g_jt_variant == 1) hipLaunchKernelGGL(json_text_emit_coop_kernel, grid, dim3(kLgThreads), 0, stream, a);
+  else hipLaunchKernelGGL(json_text_emit_lane_kernel, grid, dim3(kLgThreads), 0, stream, a);
   return hipGetLastError();
 }
 

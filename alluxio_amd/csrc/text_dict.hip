@@ -6,7 +6,8 @@
 //
 // Variant 1, cooperative: a group of 16 lanes owns a value (four values per wave).  The hash is
 // summed over steps of 256 bytes, lane l of the group taking the two words of the 16 bytes at
-// step * 256 + 16 * l, and added up with a 16-lane butterfly; the sum of terms is the same in any
+// step * 256 + 16 * l (lg_load16 of lane_group.h, as the group shuffles), and added up with a
+// 16-lane butterfly; the sum of terms is the same in any
 // order, so it equals the serial hash.  The walk: the group's lane 0 loads the slot (and claims an
 // empty one), the slot is broadcast, a candidate with an equal tag and length is compared by the
 // whole group in the same 256-byte steps with a ballot for "any lane differs", and lane 0 applies
@@ -18,74 +19,40 @@
 // No path loads a byte outside a value or an entry: a vector that reaches past the end is assembled
 // from byte loads.  All atomics are HIP's global atomics issued by vector lanes.
 #include "kernels.h"
+#include "lane_group.h"
 
 namespace amdx {
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kTdThreads = 256;
-constexpr int kTdGroup = 16;                        // lanes per value in variant 1
-constexpr int kTdValuesPerBlock = kTdThreads / kTdGroup;
-
-__global__ __launch_bounds__(kTdThreads) void text_dict_probe_lane_kernel(TextDictArgs a) {
-  const uint64_t r = (uint64_t)blockIdx.x * kTdThreads + threadIdx.x;
+__global__ __launch_bounds__(kLgThreads) void text_dict_probe_lane_kernel(TextDictArgs a) {
+  const uint64_t r = (uint64_t)blockIdx.x * kLgThreads + threadIdx.x;
   if (r < a.in.n) td_probe_one(a, r);
 }
 
-__global__ __launch_bounds__(kTdThreads) void text_dict_first_kernel(TextDictArgs a) {
-  const uint64_t r = (uint64_t)blockIdx.x * kTdThreads + threadIdx.x;
+__global__ __launch_bounds__(kLgThreads) void text_dict_first_kernel(TextDictArgs a) {
+  const uint64_t r = (uint64_t)blockIdx.x * kLgThreads + threadIdx.x;
   if (r < a.in.n) td_first_one(a, r);
 }
 
-__global__ __launch_bounds__(kTdThreads) void text_dict_codes_kernel(TextDictArgs a) {
-  const uint64_t r = (uint64_t)blockIdx.x * kTdThreads + threadIdx.x;
+__global__ __launch_bounds__(kLgThreads) void text_dict_codes_kernel(TextDictArgs a) {
+  const uint64_t r = (uint64_t)blockIdx.x * kLgThreads + threadIdx.x;
   if (r < a.in.n) td_codes_one(a, r);
 }
 
-__global__ __launch_bounds__(kTdThreads) void text_dict_commit_kernel(TextDictArgs a) {
-  const uint64_t r = (uint64_t)blockIdx.x * kTdThreads + threadIdx.x;
+__global__ __launch_bounds__(kLgThreads) void text_dict_commit_kernel(TextDictArgs a) {
+  const uint64_t r = (uint64_t)blockIdx.x * kLgThreads + threadIdx.x;
   if (r < a.in.n) td_commit_one(a, r);
 }
 
-__global__ __launch_bounds__(kTdThreads) void text_dict_rehash_kernel(TextDictArgs a) {
-  const uint64_t e = (uint64_t)blockIdx.x * kTdThreads + threadIdx.x;
+__global__ __launch_bounds__(kLgThreads) void text_dict_rehash_kernel(TextDictArgs a) {
+  const uint64_t e = (uint64_t)blockIdx.x * kLgThreads + threadIdx.x;
   if (e < a.D) td_rehash_one(a, e);
 }
 
-// The 16 bytes at p as two words, or the first rem < 16 of them from byte loads (nothing past the
-// end is read), zero padded.
-__device__ __forceinline__ void td_load16(const uint8_t* p, uint64_t rem, uint64_t* lo, uint64_t* hi) {
-  if (rem >= 16) {
-    u32x4 v;
-    __builtin_memcpy(&v, p, 16);                    // any byte phase
-    *lo = ((uint64_t)v.y << 32) | v.x;
-    *hi = ((uint64_t)v.w << 32) | v.z;
-  } else {
-    uint64_t l = 0, h = 0;
-    for (uint32_t j = 0; j < (uint32_t)rem; ++j) {
-      const uint64_t b = p[j];
-      if (j < 8) l |= b << (8 * j);
-      else h |= b << (8 * (j - 8));
-    }
-    *lo = l;
-    *hi = h;
-  }
-}
-
-__device__ __forceinline__ uint64_t td_shfl(uint64_t v, int src) {
-  const uint32_t lo = __shfl((uint32_t)v, src, kTdGroup), hi = __shfl((uint32_t)(v >> 32), src, kTdGroup);
-  return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t td_shfl_xor(uint64_t v, int d) {
-  const uint32_t lo = __shfl_xor((uint32_t)v, d, kTdGroup), hi = __shfl_xor((uint32_t)(v >> 32), d, kTdGroup);
-  return ((uint64_t)hi << 32) | lo;
-}
-
-__global__ __launch_bounds__(kTdThreads) void text_dict_probe_coop_kernel(TextDictArgs a) {
-  const uint32_t lane = threadIdx.x & 63, gl = lane & (kTdGroup - 1), g = lane / kTdGroup;
-  const uint64_t r = (uint64_t)blockIdx.x * kTdValuesPerBlock + threadIdx.x / kTdGroup;
+__global__ __launch_bounds__(kLgThreads) void text_dict_probe_coop_kernel(TextDictArgs a) {
+  const uint32_t lane = threadIdx.x & 63, gl = lane & (kLgGroup - 1), g = lane / kLgGroup;
+  const uint64_t r = (uint64_t)blockIdx.x * kLgPerBlock + threadIdx.x / kLgGroup;
   uint64_t off = 0, n = 0;
   const bool row = r < a.in.n;
   const bool live = row && tc_live(a.in, r, &off, &n);
@@ -93,18 +60,17 @@ __global__ __launch_bounds__(kTdThreads) void text_dict_probe_coop_kernel(TextDi
   const uint8_t* p = a.in.data + off;
 
   uint64_t sum = 0;
-  for (uint64_t base = 0; __ballot(base < n) != 0ull; base += kTdGroup * 16) {
+  for (uint64_t base = 0; __ballot(base < n) != 0ull; base += kLgStep) {
     const uint64_t pos = base + (uint64_t)gl * 16;
     if (pos < n) {
       const uint64_t rem = n - pos;
-      uint64_t lo, hi;
-      td_load16(p + pos, rem, &lo, &hi);
-      sum += td_term(pos / 8, lo);
-      if (rem > 8) sum += td_term(pos / 8 + 1, hi);
+      const u32x4 v = lg_load16(p + pos, rem);      // zero padded past the end
+      sum += td_term(pos / 8, lg_lo64(v));
+      if (rem > 8) sum += td_term(pos / 8 + 1, lg_hi64(v));
     }
   }
 #pragma unroll
-  for (int d = kTdGroup / 2; d; d >>= 1) sum += td_shfl_xor(sum, d);
+  for (int d = kLgGroup / 2; d; d >>= 1) sum += lg_shfl64_xor_group(sum, d);
   const uint64_t h = live ? td_finish(sum, n, a.hash_bits) : 0;
 
   const uint64_t mask = a.capacity - 1, tag = h & kTdTagMask;
@@ -121,7 +87,7 @@ __global__ __launch_bounds__(kTdThreads) void text_dict_probe_coop_kernel(TextDi
         if (v == kTdEmpty) v = mine;                // claimed; a lost race leaves what stands there now
       }
     }
-    v = td_shfl(v, 0);
+    v = lg_shfl64_group(v, 0);
     bool cand = false;
     const uint8_t* q = p;
     uint64_t qn = 0;
@@ -136,17 +102,15 @@ __global__ __launch_bounds__(kTdThreads) void text_dict_probe_coop_kernel(TextDi
       }
     }
     bool cmp = cand, differs = false;
-    for (uint64_t base = 0; __ballot(cmp && base < n) != 0ull; base += kTdGroup * 16) {
+    for (uint64_t base = 0; __ballot(cmp && base < n) != 0ull; base += kLgStep) {
       const uint64_t pos = base + (uint64_t)gl * 16;
       bool d = false;
       if (cmp && pos < n) {
         const uint64_t rem = n - pos;
-        uint64_t plo, phi, qlo, qhi;
-        td_load16(p + pos, rem, &plo, &phi);
-        td_load16(q + pos, rem, &qlo, &qhi);
-        d = plo != qlo || phi != qhi;
+        const u32x4 pv = lg_load16(p + pos, rem), qv = lg_load16(q + pos, rem);
+        d = lg_lo64(pv) != lg_lo64(qv) || lg_hi64(pv) != lg_hi64(qv);
       }
-      if ((uint32_t)(__ballot(d) >> (g * kTdGroup)) & 0xFFFFu) {
+      if (lg_group16(__ballot(d), g)) {
         differs = true;
         cmp = false;
       }
@@ -191,10 +155,10 @@ hipError_t launch_text_dict_probe(const TextDictArgs& a, hipStream_t stream) {
   if (!td_values_ok(a) || !a.table || !a.slot_of || !a.hash) return hipErrorInvalidValue;
   if (a.D && (!a.ent_off || (!a.ent_data && a.ent_bytes))) return hipErrorInvalidValue;
   if (g_td_variant == 1) {
-    hipLaunchKernelGGL(text_dict_probe_coop_kernel, dim3(td_grid(a.in.n, kTdValuesPerBlock)), dim3(kTdThreads), 0,
+    hipLaunchKernelGGL(text_dict_probe_coop_kernel, dim3(td_grid(a.in.n, kLgPerBlock)), dim3(kLgThreads), 0,
                        stream, a);
   } else {
-    hipLaunchKernelGGL(text_dict_probe_lane_kernel, dim3(td_grid(a.in.n, kTdThreads)), dim3(kTdThreads), 0, stream, a);
+    hipLaunchKernelGGL(text_dict_probe_lane_kernel, dim3(td_grid(a.in.n, kLgThreads)), dim3(kLgThreads), 0, stream, a);
   }
   return hipGetLastError();
 }
@@ -203,7 +167,7 @@ hipError_t launch_text_dict_first(const TextDictArgs& a, hipStream_t stream) {
   if (!text_dict_scalars_ok(a)) return hipErrorInvalidValue;
   if (a.in.n == 0) return hipSuccess;
   if (!a.table || !a.slot_of || !a.in.length || !a.first || !a.first_len) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(text_dict_first_kernel, dim3(td_grid(a.in.n, kTdThreads)), dim3(kTdThreads), 0, stream, a);
+  hipLaunchKernelGGL(text_dict_first_kernel, dim3(td_grid(a.in.n, kLgThreads)), dim3(kLgThreads), 0, stream, a);
   return hipGetLastError();
 }
 
@@ -211,7 +175,7 @@ hipError_t launch_text_dict_codes(const TextDictArgs& a, hipStream_t stream) {
   if (!text_dict_scalars_ok(a)) return hipErrorInvalidValue;
   if (a.in.n == 0) return hipSuccess;
   if (!a.table || !a.slot_of || !a.codes) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(text_dict_codes_kernel, dim3(td_grid(a.in.n, kTdThreads)), dim3(kTdThreads), 0, stream, a);
+  hipLaunchKernelGGL(text_dict_codes_kernel, dim3(td_grid(a.in.n, kLgThreads)), dim3(kLgThreads), 0, stream, a);
   return hipGetLastError();
 }
 
@@ -220,7 +184,7 @@ hipError_t launch_text_dict_commit(const TextDictArgs& a, hipStream_t stream) {
   if (a.in.n == 0) return hipSuccess;
   if (!a.table || !a.slot_of || !a.hash || !a.first || !a.rank || !a.byte_off || !a.ent_hash || !a.ent_off)
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(text_dict_commit_kernel, dim3(td_grid(a.in.n, kTdThreads)), dim3(kTdThreads), 0, stream, a);
+  hipLaunchKernelGGL(text_dict_commit_kernel, dim3(td_grid(a.in.n, kLgThreads)), dim3(kLgThreads), 0, stream, a);
   return hipGetLastError();
 }
 
@@ -228,7 +192,7 @@ hipError_t launch_text_dict_rehash(const TextDictArgs& a, hipStream_t stream) {
   if (!text_dict_scalars_ok(a) || a.capacity < 2 * a.D) return hipErrorInvalidValue;
   if (a.D == 0) return hipSuccess;
   if (!a.table || !a.ent_hash) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(text_dict_rehash_kernel, dim3(td_grid(a.D, kTdThreads)), dim3(kTdThreads), 0, stream, a);
+  hipLaunchKernelGGL(text_dict_rehash_kernel, dim3(td_grid(a.D, kLgThreads)), dim3(kLgThreads), 0, stream, a);
   return hipGetLastError();
 }
 

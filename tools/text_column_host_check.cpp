@@ -11,8 +11,8 @@
 // 256-byte step, quote runs that end at and straddle those edges, values of quotes only, values
 // that are not live, offsets that disagree with the data.  tc_drop16 is compared with the serial
 // rule for all 2^17 inputs, and the way kernel variant 1 hands the run parity from vector to
-// vector (nearest lower vector that is not all quotes) is replayed here in plain C++ against the
-// serial walk.  Exit status 0 and "ok" when all hold.
+// vector (nearest lower vector that is not all quotes: lg_carry_in and lg_carry_next of
+// csrc/lane_group.h, the functions the kernel calls) is replayed here against the serial walk.  Exit status 0 and "ok" when all hold.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "lane_group.h"
 #include "text_column_host.h"
 
 using namespace amdx;
@@ -118,7 +119,7 @@ static void check_values(const std::vector<std::string>& values, int quote, size
 }
 
 // Kernel variant 1 on the host: vectors of 16 bytes in steps of 16 lanes, the incoming parity of a
-// lane taken from the nearest lower lane that is not all quotes.
+// lane taken from the nearest lower lane that is not all quotes by the kernel's own two functions.
 static std::string coop(const std::string& v, int quote) {
   std::string out;
   uint32_t carry = 0;
@@ -135,13 +136,11 @@ static std::string coop(const std::string& v, int quote) {
       if (tc_carry_out16(qm[l], tc_drop16(qm[l], 0))) gb |= 1u << l;
     }
     for (uint32_t l = 0; l < 16; ++l) {
-      const uint32_t below = ga & ((1u << l) - 1u);
-      const uint32_t in = below ? (gb >> (31 - __builtin_clz(below))) & 1u : carry;
-      const uint32_t keep = valid[l] & ~tc_drop16(qm[l], in);
+      const uint32_t keep = valid[l] & ~tc_drop16(qm[l], lg_carry_in(ga, gb, l, carry));
       for (uint32_t j = 0; j < 16; ++j)
         if ((keep >> j) & 1u) out += v[base + 16 * l + j];
     }
-    if (ga) carry = (gb >> (31 - __builtin_clz(ga))) & 1u;
+    carry = lg_carry_next(ga, gb, carry);
   }
   return out;
 }
