@@ -21,6 +21,7 @@
 #include "json_fields.h"
 #include "parquet_decode.h"
 #include "parquet_encode.h"
+#include "parquet_stats.h"
 #include "text_dict.h"
 #include "kernels.h"
 #include "seg_ring.h"
@@ -875,6 +876,33 @@ PYBIND11_MODULE(_C, m) {
         py::arg("blob"), py::arg("blob_bytes"), py::arg("segs"), py::arg("nsegs"), py::arg("out"), py::arg("out_bytes"),
         py::arg("device"), py::arg("stream") = 0);
   m.def("parquet_encode_launches", &parquet_encode_launches);
+
+  // ---- Parquet column statistics (parquet_stats.cpp) --------------------------------------------
+  // The segment table (csrc/parquet_stats_host.h) holds the addresses of the columns' arrays; the
+  // result rows come back as they are and parquet_stats_finish reads one of them on the host.
+  m.def("parquet_stats_raw",
+        [](uint64_t segs, uint64_t nsegs, uint64_t mark_first, uint64_t mark_last, uint64_t text_first, uint64_t largest,
+           uint64_t alive, uint64_t flat_n, uint64_t results, int device, uint64_t stream) {
+          py::gil_scoped_release rel;
+          parquet_stats_raw(segs, nsegs, mark_first, mark_last, text_first, largest, alive, flat_n, results, device,
+                            stream);
+        },
+        py::arg("segs"), py::arg("nsegs"), py::arg("mark_first"), py::arg("mark_last"), py::arg("text_first"),
+        py::arg("largest"), py::arg("alive"), py::arg("flat_n"), py::arg("results"), py::arg("device"),
+        py::arg("stream") = 0);
+  m.def("parquet_stats_launches", &parquet_stats_launches);
+  // (min, max) of a result row in host memory as the PLAIN bytes the format stores, or (None, None).
+  m.def("parquet_stats_finish",
+        [](uint64_t row, int kind, int width, bool is_float) -> py::object {
+          if (!row) throw StoreError(kErrInvalidArgument, "parquet stats: no result row");
+          uint8_t mn[kPsTextCap], mx[kPsTextCap];
+          uint32_t nmin = 0, nmax = 0;
+          if (!ps_finish(reinterpret_cast<const int64_t*>(row), kind, (uint32_t)width, is_float, mn, &nmin, mx, &nmax))
+            return py::make_tuple(py::none(), py::none());
+          return py::make_tuple(py::bytes(reinterpret_cast<const char*>(mn), nmin),
+                                py::bytes(reinterpret_cast<const char*>(mx), nmax));
+        },
+        py::arg("row"), py::arg("kind"), py::arg("width"), py::arg("is_float"));
 
   // ---- text dictionaries (text_dict.cpp) ------------------------------------------------------
   // First-occurrence codes of unquoted text values against a dictionary whose state (table, entry

@@ -16,6 +16,7 @@
 #include "json_text_host.h"
 #include "parquet_encode_host.h"
 #include "parquet_host.h"
+#include "parquet_stats_host.h"
 #include "text_column_host.h"
 #include "text_dict_host.h"
 
@@ -264,6 +265,12 @@ int parquet_decode_variant();
 // the range has and sizes the grid.  Only addresses that the page table names are read, and nothing
 // is written outside the flat arrays, the measure table and [out, out + out_bytes).
 hipError_t launch_parquet_encode(const PeArgs& a, int pass, uint64_t largest, hipStream_t stream);
+
+// Parquet column statistics (parquet_stats.hip): pass `pass` (kPsPass*) of parquet_stats_host.h over
+// the segments [a.first, a.last), one launch; `largest` is the most rows that a segment of the range
+// has and sizes the grid.  Only addresses that the segment table names are read; writes go to the
+// result rows, the alive bytes and, in the mark pass, the mark bytes that the table names.
+hipError_t launch_parquet_stats(const PsArgs& a, int pass, uint64_t largest, hipStream_t stream);
 
 // Text dictionaries (text_dict.hip): the passes of text_dict_host.h, one launch each.  probe uses
 // global atomics on the table (compare-and-swap, min) and never waits on another lane or

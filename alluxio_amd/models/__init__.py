@@ -8,5 +8,6 @@ from .dataset import (DeviceBatchLoader, FixedRecordDataset, IndexedRecordDatase
 from .fields import (Column, FieldColumns, TextDictionary, extract_text, parse_fields,  # noqa: F401
                      read_delimited_columns, split_row)
 from .json_fields import parse_json_fields, read_json_columns, unescape_json_text  # noqa: F401
-from .parquet import (ParquetMetadata, ParquetWriter, parquet_metadata, parquet_page_table,  # noqa: F401
-                      parquet_row_groups, read_parquet_columns, write_parquet_columns)
+from .parquet import (ParquetMetadata, ParquetStatistics, ParquetWriter, column_statistics,  # noqa: F401
+                      parquet_matching_row_groups, parquet_metadata, parquet_page_table, parquet_row_groups,
+                      read_parquet_columns, write_parquet_columns)

@@ -34,7 +34,10 @@ The write side, :func:`write_parquet_columns` and :class:`ParquetWriter`, turns 
 flag per row and the sizes per page, the one readback), rank (``torch.cumsum``), emit (level bits,
 PLAIN values, text, bit-packed booleans and dictionary indices, and the host-built headers, all into
 one buffer per row group), then a footer from a small Thrift compact writer.  Uncompressed, V1 data
-pages, flat columns, no statistics.
+pages, flat columns.  ``statistics=True`` has the device compute ``null_count``, ``min_value`` and
+``max_value`` of every column chunk (``csrc/parquet_stats_host.h`` has the rules;
+:func:`column_statistics` gives them for any :class:`FieldColumns`), and the readers take
+``filters=`` to skip the row groups that the statistics of any file rule out.
 """
 from __future__ import annotations
 
@@ -56,7 +59,8 @@ ENCODINGS = {0: "PLAIN", 2: "PLAIN_DICTIONARY", 3: "RLE", 4: "BIT_PACKED", 5: "D
 ParquetLeaf = namedtuple("ParquetLeaf", "name physical_type repetition max_definition_level max_repetition_level "
                                         "type_length")
 ParquetChunk = namedtuple("ParquetChunk", "name physical_type codec num_values dictionary_page_offset "
-                                          "data_page_offset total_compressed_size")
+                                          "data_page_offset total_compressed_size statistics", defaults=(None,))
+ParquetStatistics = namedtuple("ParquetStatistics", "null_count min max")
 ParquetRowGroup = namedtuple("ParquetRowGroup", "num_rows columns")
 ParquetMetadata = namedtuple("ParquetMetadata", "num_rows schema row_groups created_by")
 
@@ -169,14 +173,73 @@ def _name(codes, i):
     return codes[i] if isinstance(i, int) and 0 <= i < len(codes) else f"UNKNOWN({i})"
 
 
+# converted types and LogicalType union fields whose order is that of the physical type as our column
+# types see it: UTF8, ENUM, DATE, TIME_*, TIMESTAMP_*, INT_8 .. INT_64, JSON; STRING, ENUM, DATE, TIME,
+# TIMESTAMP, INTEGER (signed only), JSON
+_OUR_CONVERTED = {0, 4, 6, 7, 8, 9, 10, 15, 16, 17, 18, 19}
+_OUR_LOGICAL = {1, 4, 6, 7, 8, 10, 12}
+_PLAIN_FORMAT = {"INT32": "<i", "INT64": "<q", "FLOAT": "<f", "DOUBLE": "<d"}
+
+
+def _our_order(elem: dict) -> bool:
+    """Whether min_value / max_value of a leaf (its SchemaElement) are in the order in which our
+    column types compare: signed integers, IEEE floats, unsigned bytes."""
+    conv, logical = elem.get(6), elem.get(10)
+    if conv is not None and conv not in _OUR_CONVERTED:
+        return False
+    if logical is not None:
+        if not isinstance(logical, dict) or len(logical) != 1 or next(iter(logical)) not in _OUR_LOGICAL:
+            return False
+        if 10 in logical and not (isinstance(logical[10], dict) and logical[10].get(2) is True):
+            return False                                # an unsigned INTEGER
+    return True
+
+
+def _stat_value(physical: str, raw):
+    """A PLAIN-encoded statistics value as a Python value; ``None`` when the bytes do not fit the type."""
+    if not isinstance(raw, bytes):
+        return None
+    if physical == "BYTE_ARRAY":
+        return raw
+    if physical == "BOOLEAN":
+        return bool(raw[0]) if len(raw) == 1 else None
+    fmt = _PLAIN_FORMAT.get(physical)
+    if fmt is None or len(raw) != struct.calcsize(fmt):
+        return None
+    return struct.unpack(fmt, raw)[0]
+
+
+def _read_statistics(st, physical: str, ordered: bool):
+    """The ``Statistics`` struct of a column chunk (``None`` without one) as ParquetStatistics."""
+    if not isinstance(st, dict):
+        return None
+    lo = hi = None
+    if ordered:
+        lo, hi = _stat_value(physical, st.get(6)), _stat_value(physical, st.get(5))
+        if lo is None or hi is None or lo != lo or hi != hi:        # one bound alone, or a NaN, says nothing
+            lo = hi = None
+    nulls = st.get(3)
+    return ParquetStatistics(nulls if isinstance(nulls, int) and not isinstance(nulls, bool) else None, lo, hi)
+
+
 def parquet_metadata(fs, path: str) -> ParquetMetadata:
     """The footer of a Parquet file, read with positioned reads through the client stream (the last
     8 bytes, then the ``FileMetaData``): ``num_rows``, ``schema`` (one :class:`ParquetLeaf` per leaf
     column: dotted ``name``, ``physical_type``, ``repetition``, ``max_definition_level``,
     ``max_repetition_level``, ``type_length``) and ``row_groups`` (``num_rows`` and, per leaf in
     schema order, a :class:`ParquetChunk`: ``codec``, ``num_values``, ``dictionary_page_offset``
-    (``None`` without one), ``data_page_offset``, ``total_compressed_size``).  Type, codec and
-    repetition are the names of the format specification.  Unknown fields are skipped."""
+    (``None`` without one), ``data_page_offset``, ``total_compressed_size``, ``statistics``).  Type,
+    codec and repetition are the names of the format specification.  Unknown fields are skipped.
+
+    ``statistics`` is ``None`` for a chunk without a ``Statistics`` struct (a file written without
+    statistics), else a :class:`ParquetStatistics`: ``null_count`` (``None`` if the struct has
+    none) and ``min`` / ``max`` from ``min_value`` / ``max_value`` as ``int``, ``float``, ``bool``
+    or ``bytes``.  The bounds are taken only where the file's ``column_orders`` gives the leaf the
+    type-defined order and that order is the one our column types use: a leaf without converted or
+    logical type, or STRING / UTF8, ENUM, JSON, a signed INTEGER, DATE, TIME or TIMESTAMP.  For
+    every other leaf (unsigned integers, DECIMAL, FLOAT16, INTERVAL, unknown types), for bytes that
+    do not fit the physical type and for a NaN bound they are ``None``.  The deprecated ``min`` /
+    ``max`` fields are never read."""
     length = int(fs.get_status(path).length)
     with fs.open_file(path) as f:
         if length < 12:
@@ -197,7 +260,7 @@ def parquet_metadata(fs, path: str) -> ParquetMetadata:
     if 8 in md:
         raise NotImplementedError(f"{path}: encrypted Parquet files (encrypted columns) are not supported")
     elems = md.get(2) or []
-    leaves = []
+    leaves, ours = [], []                               # ours: the leaf's order is the one our types use
 
     def walk(i, prefix, d, r):                          # depth first; returns the next element
         e = elems[i]
@@ -210,6 +273,7 @@ def parquet_metadata(fs, path: str) -> ParquetMetadata:
         if not kids:
             leaves.append(ParquetLeaf(".".join(full), _name(PHYSICAL, e.get(1)), _name(REPETITION, rep), d, r,
                                       e.get(2)))
+            ours.append(_our_order(e))
             return i
         for _ in range(kids):
             i = walk(i, full, d, r)
@@ -222,17 +286,21 @@ def parquet_metadata(fs, path: str) -> ParquetMetadata:
                 i = walk(i, [], 0, 0)
         except IndexError:
             raise ValueError(f"{path}: the schema names more children than it has elements") from None
+    orders = md.get(7) if isinstance(md.get(7), list) else []
     groups = []
     for rg in md.get(4) or []:
         cols = []
-        for cc in rg.get(1) or []:
+        for j, cc in enumerate(rg.get(1) or []):
             m = cc.get(3)
             if m is None:
                 raise NotImplementedError(f"{path}: a column chunk without metadata (encrypted, or in another file) "
                                           f"is not supported")
             cols.append(ParquetChunk(".".join(x.decode("utf-8", "replace") for x in m.get(3) or []),
                                      _name(PHYSICAL, m.get(1)), _name(CODECS, m.get(4)), m.get(5, 0), m.get(11),
-                                     m.get(9, 0), m.get(7, 0)))
+                                     m.get(9, 0), m.get(7, 0),
+                                     _read_statistics(m.get(12), _name(PHYSICAL, m.get(1)),
+                                                      j < len(ours) and ours[j] and j < len(orders)
+                                                      and isinstance(orders[j], dict) and 1 in orders[j])))
         groups.append(ParquetRowGroup(rg.get(3, 0), cols))
     return ParquetMetadata(md.get(3, 0), leaves, groups, (md.get(6) or b"").decode("utf-8", "replace"))
 
@@ -305,6 +373,111 @@ def _chunk_range(cc: ParquetChunk):
     if cc.dictionary_page_offset is not None and 0 < cc.dictionary_page_offset < start:
         start = cc.dictionary_page_offset
     return int(start), int(start) + int(cc.total_compressed_size)
+
+
+# ---- pruning row groups by their statistics -------------------------------------------------------------
+_FILTER_OPS = ("==", "!=", "<", "<=", ">", ">=", "in", "is_null")
+_INT_TYPES, _FLOAT_TYPES = ("INT32", "INT64"), ("FLOAT", "DOUBLE")
+
+
+def _filter_value(path, leaf: ParquetLeaf, v):
+    """A filter's value as what the leaf's statistics compare with, or TypeError."""
+    ph, ok = leaf.physical_type, True
+    if ph in _INT_TYPES:
+        ok = isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+        v = int(v) if ok else v
+    elif ph in _FLOAT_TYPES:
+        ok = isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+    elif ph == "BOOLEAN":
+        ok = isinstance(v, (bool, np.bool_))
+        v = bool(v) if ok else v
+    elif ph == "BYTE_ARRAY":
+        ok = isinstance(v, (bytes, str))
+        v = v.encode("utf-8") if isinstance(v, str) else v
+    if not ok:
+        raise TypeError(f"{path}: a filter on column {leaf.name!r} ({ph}) cannot take the value {v!r}")
+    return v
+
+
+def _filters(path, md: ParquetMetadata, filters):
+    """``filters`` as a list of alternatives, each a list of (leaf position, op, value), checked."""
+    if filters is None:
+        return None
+    filters = list(filters)
+    if filters and all(isinstance(f, tuple) for f in filters):
+        filters = [filters]
+    by_name = {lf.name: j for j, lf in enumerate(md.schema)}
+    out = []
+    for alt in filters:
+        terms = []
+        for term in alt:
+            if not isinstance(term, (tuple, list)) or len(term) != 3:
+                raise ValueError(f"a filter is (leaf name, op, value), got {term!r}")
+            leaf, op, v = term
+            if leaf not in by_name:
+                raise KeyError(f"{path}: no column {leaf!r} to filter on; the leaves are {sorted(by_name)}")
+            op = "==" if op == "=" else op
+            if op not in _FILTER_OPS:
+                raise ValueError(f"unknown filter op {op!r}: one of {', '.join(_FILTER_OPS)}")
+            j = by_name[leaf]
+            lf = md.schema[j]
+            if op == "is_null":
+                if not isinstance(v, (bool, np.bool_)):
+                    raise TypeError(f"{path}: is_null on column {leaf!r} takes True or False, not {v!r}")
+                v = bool(v)
+            elif op == "in":
+                if isinstance(v, (str, bytes)) or not hasattr(v, "__iter__"):
+                    raise TypeError(f"{path}: 'in' on column {leaf!r} takes a collection, not {v!r}")
+                v = [_filter_value(path, lf, x) for x in v]
+            else:
+                v = _filter_value(path, lf, v)
+            terms.append((j, op, v))
+        out.append(terms)
+    return out
+
+
+def _may_match(cc: ParquetChunk, op: str, v) -> bool:
+    """False only when the chunk's statistics prove that no row of it satisfies ``op v``."""
+    st = cc.statistics
+    if st is None:
+        return True
+    all_null = st.null_count is not None and st.null_count == cc.num_values
+    if op == "is_null":
+        return st.null_count is None or (st.null_count != 0 if v else not all_null)
+    lo, hi = st.min, st.max
+    if op == "!=":                                      # NaNs are outside the bounds and satisfy !=
+        return not (lo is not None and lo == hi == v and cc.physical_type not in _FLOAT_TYPES)
+    if all_null:
+        return False
+    if lo is None or hi is None:
+        return True
+    vs = v if op == "in" else [v]
+    if any(x != x for x in vs):                         # a NaN to compare with: nothing is proven
+        return True
+    if op in ("==", "in"):
+        return any(lo <= x <= hi for x in vs)
+    return {"<": lo < v, "<=": lo <= v, ">": hi > v, ">=": hi >= v}[op]
+
+
+def _matching(path, md: ParquetMetadata, filters, row_groups):
+    n = len(md.row_groups)
+    groups = list(range(n)) if row_groups is None else [int(g) for g in row_groups]
+    for g in groups:
+        if not 0 <= g < n:
+            raise IndexError(f"{path}: no row group {g} (there are {n})")
+    if not filters:
+        return groups
+    return [g for g in groups
+            if any(all(j >= len(md.row_groups[g].columns) or _may_match(md.row_groups[g].columns[j], op, v)
+                       for j, op, v in alt) for alt in filters)]
+
+
+def parquet_matching_row_groups(fs, path: str, filters, row_groups=None) -> list:
+    """The numbers of the row groups (of ``row_groups``, in its order; ``None``: all) that the
+    file's statistics cannot rule out for ``filters``: what :func:`read_parquet_columns` reads when
+    given the same filters.  Only the footer is read."""
+    md = parquet_metadata(fs, path)
+    return _matching(path, md, _filters(path, md, filters), row_groups)
 
 
 # ---- the passes ---------------------------------------------------------------------------------------
@@ -693,13 +866,16 @@ def _row_group(path, dl, records, sizes, rg, specs, dicts):
 
 
 def parquet_row_groups(fs, path: str, columns=None, row_groups=None, device=None, device_plan="auto",
-                       dictionaries=None):
+                       dictionaries=None, filters=None):
     """A generator of one :class:`FieldColumns` per row group (``row_groups``: their numbers, in the
-    order wanted; ``None``: all), for a training loop that takes a file piece by piece.  Arguments
-    are those of :func:`read_parquet_columns`; a category column's dictionary is shared by all row
-    groups.  The footer is read and everything it can refuse is refused when the generator is
-    created, not at the first ``next``."""
+    order wanted; ``None``: all; with ``filters``, those of them that the statistics cannot rule
+    out), for a training loop that takes a file piece by piece.  Arguments are those of
+    :func:`read_parquet_columns`; a category column's dictionary is shared by all row groups.  The
+    footer is read and everything it can refuse is refused when the generator is created, not at the
+    first ``next``."""
     md = parquet_metadata(fs, path)
+    if filters is not None:
+        row_groups = _matching(path, md, _filters(path, md, filters), row_groups)
     specs, groups = _plan(path, md, columns, row_groups)
     return _row_group_iter(fs, path, md, specs, groups, device, device_plan, dictionaries)
 
@@ -734,7 +910,7 @@ def _row_group_iter(fs, path, md, specs, groups, device, device_plan, dictionari
 
 
 def read_parquet_columns(fs, path: str, columns=None, row_groups=None, device=None, device_plan="auto",
-                         dictionaries=None) -> FieldColumns:
+                         dictionaries=None, filters=None) -> FieldColumns:
     """The selected columns of a Parquet file as tensors on ``device``, decoded where the bytes lie.
 
     ``columns``: ``None`` (every supported leaf, with the type its physical type implies), a list of
@@ -746,6 +922,20 @@ def read_parquet_columns(fs, path: str, columns=None, row_groups=None, device=No
     column's name to the :class:`TextDictionary` to encode into, so codes
     agree across files; a category column without one gets a fresh dictionary for the file.
 
+    ``filters`` prunes whole row groups by the statistics in the footer (:func:`parquet_metadata`):
+    a list of ``(leaf name, op, value)`` that must all hold, or a list of such lists of which any
+    may hold (pyarrow's form).  The ops are ``==`` (also ``=``), ``!=``, ``<``, ``<=``, ``>``,
+    ``>=``, ``in`` (a collection) and ``is_null`` (``True`` or ``False``); a value is an ``int`` for
+    an integer column, an ``int`` or ``float`` for a float column, a ``bool`` for a boolean column
+    and ``bytes`` or ``str`` (taken as UTF-8) for a BYTE_ARRAY column, else ``TypeError``; an unknown
+    leaf is a ``KeyError``, an unknown op a ``ValueError``, all before any data is read.  The leaf
+    need not be among ``columns``.  A row group is skipped only when its statistics prove that no
+    row of it can match (a chunk without statistics, or without bounds, keeps its row group), and a
+    row group that is kept comes back whole: rows are not filtered.  The bytes of a skipped row
+    group are never gathered and none of its pages is walked, and what the footer refuses (codec,
+    nesting, physical type) is refused for the kept row groups only.  With every row group pruned the
+    result has no rows, the requested columns and types, and nothing is gathered or launched.
+
     The bytes of the selected column chunks, and only those, come through a
     :class:`DeviceBatchLoader` over the file cut at chunk boundaries: one ragged gather per row group
     when the file is cached in device memory by one in-process worker (``device_plan="auto"``); a
@@ -753,7 +943,7 @@ def read_parquet_columns(fs, path: str, columns=None, row_groups=None, device=No
     row group the page table, a flag per LZ4 page and the sizes that text columns, dictionaries and
     (in kernel variant 1) run tables need are read back; everything else stays on torch's current
     stream.  See the module's documentation for types, statuses and what is refused."""
-    parts = list(parquet_row_groups(fs, path, columns, row_groups, device, device_plan, dictionaries))
+    parts = list(parquet_row_groups(fs, path, columns, row_groups, device, device_plan, dictionaries, filters))
     return FieldColumns.concat(parts)
 
 
@@ -900,13 +1090,118 @@ def _write_columns(columns, required):
     return out, dev
 
 
+# segment-table and result columns of csrc/parquet_stats_host.h
+_E_ISFLOAT, _E_MARK = 13, 14
+_SR_COLS, _S_NULLS, _S_MIN, _S_MAX, _S_ROUND_MIN, _S_ROUNDS = 28, 0, 2, 3, 8, 10
+
+
+class _StatsPlan:
+    """The statistics of rows [r0, r0 + n) of the writer's columns, one segment per column (and one
+    per category column's dictionary): the segment table and the result rows as they start, both
+    on the host, and the device arrays the passes need."""
+    __slots__ = ("cols", "dev", "table", "init", "seg", "dict_seg", "mark_range", "text_first", "largest", "alive", "marks")
+
+    def __init__(self, cols, r0, n, dev):
+        import torch
+        self.cols, self.dev = cols, dev
+        order = sorted(range(len(cols)), key=lambda j: (_KIND_ORDER[cols[j].kind], j))
+        cats = [j for j in order if cols[j].kind == _K_INDEX]
+        entries = [len(cols[j].dictionary) for j in cats]
+        self.marks = torch.ones(sum(entries), dtype=torch.uint8, device=dev) if cats else None
+        self.table = np.zeros((len(cols) + len(cats), _PE_COLS), dtype=np.int64)
+        self.seg, self.dict_seg = {}, {}
+        flat = mark_at = 0
+        for s, j in enumerate(order):
+            c, row = cols[j], self.table[s]
+            self.seg[j] = s
+            row[_E_KIND], row[_E_WIDTH] = c.kind, c.width
+            row[_E_VALUES], row[_E_STATUS] = _ptr(c.values), c.status.data_ptr() if n else 0
+            row[_E_OFFSETS] = c.offsets.data_ptr() if c.offsets is not None else 0
+            row[_E_AUX] = c.data_bytes if c.kind == _K_TEXT else len(c.dictionary) if c.kind == _K_INDEX else 0
+            row[_E_ROW], row[_E_ROWS], row[_E_LEVEL] = r0, n, -1
+            row[_E_ISFLOAT] = c.type in (FLOAT32, FLOAT64)
+            if c.kind == _K_TEXT:
+                row[_E_FLAT] = flat
+                flat += n
+        for k, j in enumerate(cats):                    # the dictionaries: text segments whose status is the marks
+            d, row = cols[j].dictionary, self.table[len(cols) + k]
+            self.dict_seg[j] = len(cols) + k
+            mark = self.marks.data_ptr() + mark_at if entries[k] else 0
+            self.table[self.seg[j], _E_MARK] = mark
+            row[_E_KIND], row[_E_VALUES], row[_E_OFFSETS] = _K_TEXT, _ptr(d._data), d._off.data_ptr()
+            row[_E_STATUS], row[_E_AUX], row[_E_ROWS], row[_E_LEVEL] = mark, d._nbytes, entries[k], -1
+            row[_E_FLAT] = flat
+            flat += entries[k]
+            mark_at += entries[k]
+        kinds = self.table[:, _E_KIND]
+        marked = np.nonzero(kinds == _K_INDEX)[0]
+        self.mark_range = (int(marked[0]), int(marked[-1]) + 1) if len(marked) else (0, 0)
+        texts = np.nonzero(kinds == _K_TEXT)[0]
+        self.text_first = int(texts[0]) if len(texts) else len(self.table)
+        self.largest = int(self.table[:, _E_ROWS].max())
+        self.alive = torch.empty(flat, dtype=torch.uint8, device=dev) if flat else None
+        self.init = np.zeros((len(self.table), _SR_COLS), dtype=np.int64)
+        self.init[:, _S_MIN], self.init[:, _S_MAX] = np.iinfo(np.int64).max, np.iinfo(np.int64).min
+        self.init[:, _S_ROUND_MIN:_S_ROUND_MIN + _S_ROUNDS] = -1
+
+    def launch(self, d_table: int, d_results: int) -> None:
+        """All passes, queued: ``d_table`` and ``d_results`` are where ``table`` and ``init`` lie on the device."""
+        from ..ops.native import lib, native_errors
+        device, stream = _queue(self.dev)
+        with native_errors():
+            lib().parquet_stats_raw(d_table, len(self.table), *self.mark_range, self.text_first, self.largest,
+                                    _ptr(self.alive), 0 if self.alive is None else self.alive.numel(), d_results, device,
+                                    stream)
+
+    def finish(self, results: np.ndarray) -> list:
+        """Per column ``(null_count, min, max)`` with the bounds as PLAIN bytes or ``None``, from the
+        result rows on the host."""
+        from ..ops.native import lib
+        C = lib()
+        results = np.ascontiguousarray(results, dtype=np.int64)
+        out = []
+        for j, c in enumerate(self.cols):
+            s = self.seg[j]
+            if c.kind == _K_INDEX:
+                lo, hi = C.parquet_stats_finish(results[self.dict_seg[j]].ctypes.data, _K_TEXT, 0, False)
+            else:
+                lo, hi = C.parquet_stats_finish(results[s].ctypes.data, c.kind, c.width, c.type in (FLOAT32, FLOAT64))
+            out.append((int(results[s, _S_NULLS]), lo, hi))
+        return out
+
+
+def column_statistics(columns) -> list:
+    """One :class:`ParquetStatistics` per column of a :class:`FieldColumns` (on a GPU or on the
+    CPU), computed where the columns lie, over all rows as one segment: what
+    ``write_parquet_columns(..., statistics=True)`` writes for a file of one row group.
+
+    ``null_count`` counts the rows that the writer would write as nulls under ``invalid="null"``:
+    every row whose status is not 0, a text value outside its data, a code outside its dictionary.
+    ``min`` and ``max`` are ``None`` without a value.  Integers compare signed and ``False`` is less
+    than ``True``.  Floats: NaNs take no part (only NaNs: no bounds), a minimum that equals zero is
+    ``-0.0`` and a maximum that equals zero ``+0.0``.  Text and category values (``bytes``) compare
+    byte by byte, unsigned, a proper prefix first; a category's bounds are taken over the dictionary
+    entries that some row uses; with a value (a used entry) longer than 64 bytes there are no
+    bounds.  One small readback."""
+    cols, dev = _write_columns(columns, ())
+    plan = _StatsPlan(cols, 0, columns.rows, dev)
+    both = _dev_i64(np.concatenate([plan.table.ravel(), plan.init.ravel()]), dev)
+    plan.launch(both.data_ptr(), both[plan.table.size:].data_ptr())
+    got = plan.finish(both[plan.table.size:].cpu().numpy().reshape(-1, _SR_COLS))
+    return [ParquetStatistics(nulls, _stat_value(c.physical, lo), _stat_value(c.physical, hi))
+            for c, (nulls, lo, hi) in zip(cols, got)]
+
+
 class _Group:
     """One row group on its way: the page table, the flat arrays and the measure table."""
-    __slots__ = ("cols", "r0", "rows", "dev", "table", "index", "flags", "text_bytes", "measure", "flat_n", "layout")
+    __slots__ = ("cols", "r0", "rows", "dev", "table", "index", "flags", "text_bytes", "measure", "flat_n", "layout",
+                 "stats")
 
 
-def _measure_group(cols, r0, r1, page_rows, dev) -> _Group:
-    """The measure pass over rows [r0, r1) of the columns: one launch and the one readback."""
+def _measure_group(cols, r0, r1, page_rows, dev, statistics=False) -> _Group:
+    """The measure pass over rows [r0, r1) of the columns: one launch and the one readback.  With
+    ``statistics`` the statistics passes are queued behind it and their result rows come back in
+    that readback: ``g.stats`` then holds ``(null_count, min, max)`` per column."""
     import torch
     from ..ops.native import lib, native_errors
     g = _Group()
@@ -933,9 +1228,24 @@ def _measure_group(cols, r0, r1, page_rows, dev) -> _Group:
     g.flat_n = len(cols) * n
     g.flags = torch.empty(g.flat_n, dtype=torch.uint8, device=dev)
     g.text_bytes = torch.empty(g.flat_n, dtype=torch.int32, device=dev) if any(c.kind == _K_TEXT for c in cols) else None
+    device, stream = _queue(dev)
+    g.stats = None
+    if statistics:                                      # both tables and both results: one copy each way
+        plan = _StatsPlan(cols, r0, n, dev)
+        m0 = np.zeros((len(g.table), _PM_COLS), dtype=np.int64)
+        m0[:, _M_MAXCODE] = -1
+        both = _dev_i64(np.concatenate([g.table.ravel(), plan.table.ravel(), m0.ravel(), plan.init.ravel()]), dev)
+        a, b = g.table.size, g.table.size + plan.table.size
+        with native_errors():
+            lib().parquet_encode_measure_raw(both.data_ptr(), len(g.table), 0, len(g.table), pr, g.flags.data_ptr(),
+                                             _ptr(g.text_bytes), g.flat_n, both[b:].data_ptr(), device, stream)
+        plan.launch(both[a:].data_ptr(), both[b + m0.size:].data_ptr())
+        host = both[b:].cpu().numpy()
+        g.measure = host[:m0.size].reshape(-1, _PM_COLS)
+        g.stats = plan.finish(host[m0.size:].reshape(-1, _SR_COLS))
+        return g
     measure = torch.zeros(len(g.table), _PM_COLS, dtype=torch.int64, device=dev)
     measure[:, _M_MAXCODE] = -1
-    device, stream = _queue(dev)
     d_table = _dev_i64(g.table, dev)
     with native_errors():
         lib().parquet_encode_measure_raw(d_table.data_ptr(), len(g.table), 0, len(g.table), pr, g.flags.data_ptr(),
@@ -1075,14 +1385,14 @@ class ParquetWriter:
     which :attr:`metadata` holds what :func:`parquet_metadata` would read.  See
     :func:`write_parquet_columns` for the format."""
 
-    def __init__(self, fs, path: str, required=(), page_rows=None, invalid="error", write_type=None):
+    def __init__(self, fs, path: str, required=(), page_rows=None, invalid="error", write_type=None, statistics=False):
         if invalid not in ("error", "null"):
             raise ValueError("invalid is 'error' or 'null'")
         if page_rows is not None and int(page_rows) < 1:
             raise ValueError("page_rows is at least 1")
         self.fs, self.path = fs, path
         self.required = (required,) if isinstance(required, str) else tuple(required)
-        self.page_rows, self.invalid, self.write_type = page_rows, invalid, write_type
+        self.page_rows, self.invalid, self.write_type, self.statistics = page_rows, invalid, write_type, bool(statistics)
         self.metadata = None
         self._schema, self._cols, self._f, self._groups, self._rows, self._closed = None, None, None, [], 0, False
         self._offsets = {}
@@ -1126,7 +1436,7 @@ class ParquetWriter:
         step = rows if row_group_rows is None else int(row_group_rows)
         groups = []
         for r0 in range(0, rows, max(step, 1)):
-            g = _measure_group(cols, r0, min(rows, r0 + step), self.page_rows, dev)
+            g = _measure_group(cols, r0, min(rows, r0 + step), self.page_rows, dev, self.statistics)
             _layout_group(g, self.invalid, self._dict_offsets)
             groups.append(g)
         self._schema, self._cols = schema, [(c.name, c.physical, c.kind, c.required) for c in cols]
@@ -1137,7 +1447,7 @@ class ParquetWriter:
                 torch.cuda.current_stream(dev).synchronize()
             base = self._f.tell()
             self._f.write(out)
-            self._groups.append((g.rows, base, int(out.numel()), g.layout[4]))
+            self._groups.append((g.rows, base, int(out.numel()), g.layout[4], g.stats))
             self._rows += g.rows
 
     def _footer(self) -> bytes:
@@ -1163,10 +1473,10 @@ class ParquetWriter:
             t.end()
         t.i64(3, self._rows)
         t.list_(4, 12, len(self._groups))
-        for rows, base, size, chunks in self._groups:
+        for rows, base, size, chunks, stats in self._groups:
             t.struct()
             t.list_(1, 12, len(chunks))
-            for (name, physical, kind, required), (dict_off, data_off, total, enc) in zip(self._cols, chunks):
+            for j, ((name, physical, kind, required), (dict_off, data_off, total, enc)) in enumerate(zip(self._cols, chunks)):
                 t.struct()
                 t.i64(2, base + (data_off if dict_off is None else dict_off))
                 t.struct(3)
@@ -1184,6 +1494,14 @@ class ParquetWriter:
                 t.i64(9, base + data_off)
                 if dict_off is not None:
                     t.i64(11, base + dict_off)
+                if stats is not None:                   # Statistics: null_count, max_value, min_value
+                    nulls, lo, hi = stats[j]
+                    t.struct(12)
+                    t.i64(3, nulls)
+                    if lo is not None:
+                        t.binary(5, hi)
+                        t.binary(6, lo)
+                    t.end()
                 t.end()
                 t.end()
             t.i64(2, size)
@@ -1192,6 +1510,13 @@ class ParquetWriter:
             t.i64(6, size)
             t.end()
         t.binary(6, CREATED_BY.encode())
+        if self.statistics:                             # column_orders: TypeDefinedOrder for every leaf
+            t.list_(7, 12, len(self._cols))
+            for _ in self._cols:
+                t.struct()
+                t.struct(1)
+                t.end()
+                t.end()
         t.end()
         return bytes(t.b)
 
@@ -1209,10 +1534,16 @@ class ParquetWriter:
         self._f.close()
         leaves = [ParquetLeaf(name, physical, "REQUIRED" if required else "OPTIONAL", 0 if required else 1, 0, None)
                   for name, physical, _kind, required in self._cols]
+
+        def read_back(physical, st):                    # what parquet_metadata makes of the bytes in the footer
+            return None if st is None else ParquetStatistics(st[0], _stat_value(physical, st[1]), _stat_value(physical, st[2]))
+
         groups = [ParquetRowGroup(rows, [ParquetChunk(name, physical, "UNCOMPRESSED", rows,
-                                                      None if d is None else base + d, base + o, total)
-                                         for (name, physical, _k, _r), (d, o, total, _e) in zip(self._cols, chunks)])
-                  for rows, base, _size, chunks in self._groups]
+                                                      None if d is None else base + d, base + o, total,
+                                                      read_back(physical, stats and stats[j]))
+                                         for j, ((name, physical, _k, _r), (d, o, total, _e))
+                                         in enumerate(zip(self._cols, chunks))])
+                  for rows, base, _size, chunks, stats in self._groups]
         self.metadata = ParquetMetadata(self._rows, leaves, groups, CREATED_BY)
 
     def abort(self) -> None:
@@ -1224,7 +1555,7 @@ class ParquetWriter:
 
 
 def write_parquet_columns(fs, path: str, columns, row_group_rows=None, page_rows=None, required=(), invalid="error",
-                          write_type=None) -> ParquetMetadata:
+                          write_type=None, statistics=False) -> ParquetMetadata:
     """Writes ``columns`` (a :class:`FieldColumns` on a GPU or on the CPU) as the Parquet file
     ``path`` and returns its metadata.  The pages are encoded where the columns lie and each row
     group's bytes go to the output stream as one tensor on that device.
@@ -1236,17 +1567,28 @@ def write_parquet_columns(fs, path: str, columns, row_group_rows=None, page_rows
     dictionary's entries up to the largest code that the row group uses, and RLE_DICTIONARY data
     pages of one bit-packed run.  Columns are OPTIONAL (status 1 is a null; definition levels are one
     RLE run for a page without nulls, else one bit-packed run) unless named in ``required``.  Data
-    pages are V1, nothing is compressed and no statistics are written.
+    pages are V1 and nothing is compressed.
 
     Refused before the file is created: a ``span`` column (``TypeError``); a status above 1, a
     deferred float included, unless ``invalid="null"`` writes such rows as nulls; a null in a
     required column; a live code outside its dictionary; a page or chunk of 2^31 bytes or more (all
     ``ValueError``).
 
+    ``statistics=True`` adds a ``Statistics`` struct to every column chunk (``null_count``, and
+    ``min_value`` / ``max_value`` where :func:`column_statistics` gives bounds: PLAIN-encoded, so a
+    text bound has no length prefix and a boolean is one byte) and ``column_orders`` to the footer,
+    so that other readers can skip row groups; page headers carry none.  A chunk with a text value
+    (or a used dictionary entry) of more than 64 bytes has a null count and no bounds.  The default
+    writes exactly the file that was written before there were statistics.
+
     Per row group: one measure launch and one small readback (the sizes of the pages, which the
     host needs for the page headers), two ``torch.cumsum`` and up to four emit launches, however many
-    columns there are; a category column's dictionary offsets are read once more when it has grown."""
-    w = ParquetWriter(fs, path, required=required, page_rows=page_rows, invalid=invalid, write_type=write_type)
+    columns there are; a category column's dictionary offsets are read once more when it has grown.
+    With statistics: one more launch for numbers alone, ten with a text column and eleven with a
+    category column (``csrc/parquet_stats.hip``), queued behind the measure launch, and their results
+    come back in that one readback."""
+    w = ParquetWriter(fs, path, required=required, page_rows=page_rows, invalid=invalid, write_type=write_type,
+                      statistics=statistics)
     try:
         w.write(columns, row_group_rows)
         w.close()

@@ -20,6 +20,12 @@ LZ4_RAW, from one process:
     client stream plus ``.to(device)`` of every column (strings as their dictionary codes), by the
     host clock around a device synchronise.  The host side never touches the code under test.
 
+(d) pruning (``--prune-groups N``, alone: the other phases are skipped): a cached file of N row
+    groups of ``--rows`` rows of the numeric columns plus a sorted int64 key, written by pyarrow
+    with statistics; ``read_parquet_columns`` with a filter on the key that keeps one row group
+    against the same read without a filter, alternating, by the host clock around a device
+    synchronise, with the bytes the gather fetched and the decode launches of each.
+
 Before timing, every column is compared with ``pq.read_table``.  One JSON line per measurement goes
 to stdout and to ``--out``.  Needs a GPU: it fails without one.
 """
@@ -251,6 +257,57 @@ def e2e_phase(torch, fs, a):
               "speedup": spread([h / o for h, o in zip(t_host, t_ours)], 2)}, a.out)
 
 
+def prune_phase(torch, C, fs, a):
+    import pyarrow as pa
+    import pyarrow.parquet as pq
+
+    from alluxio_amd.models import dataset, parquet_matching_row_groups, read_parquet_columns
+    n = a.prune_groups * a.rows
+    tbl = numeric_table(pa, n, 7).append_column("key", pa.array(np.arange(n, dtype=np.int64) * 3, pa.int64()))
+    blob = write(pq, tbl, False, a.rows)
+    path = "/bench/prune.parquet"
+    fs.write_file(path, blob, write_type="MUST_CACHE")
+    keep = a.prune_groups // 2
+    lo, hi = keep * a.rows * 3, (keep + 1) * a.rows * 3
+    filt = [("key", ">=", lo), ("key", "<", hi)]
+    if parquet_matching_row_groups(fs, path, filt) != [keep]:
+        raise SystemExit("the filter does not keep exactly one row group")
+    got = read_parquet_columns(fs, path, filters=filt, device=a.device)
+    compare(got, tbl.slice(keep * a.rows, a.rows))
+    fetched = [0]
+    gather = dataset.DeviceBatchLoader.gather
+
+    def counted(self, records):
+        batch = gather(self, records)
+        fetched[0] += int(batch.lengths.sum())
+        return batch
+
+    def read(filters):
+        fetched[0] = 0
+        before = C.parquet_decode_launches()
+        a.sync()
+        t0 = time.perf_counter()
+        read_parquet_columns(fs, path, filters=filters, device=a.device)
+        a.sync()
+        return 1e3 * (time.perf_counter() - t0), fetched[0], C.parquet_decode_launches() - before
+
+    dataset.DeviceBatchLoader.gather = counted
+    try:
+        runs = {"filtered": [], "all": []}
+        for r in range(a.warmup + a.rounds):
+            for name in (("filtered", "all") if r % 2 == 0 else ("all", "filtered")):
+                out = read(filt if name == "filtered" else None)
+                if r >= a.warmup:
+                    runs[name].append(out)
+    finally:
+        dataset.DeviceBatchLoader.gather = gather
+    rec = {"phase": "prune", "row_groups": a.prune_groups, "rows_per_group": a.rows, "file_bytes": len(blob), "unit": "ms"}
+    for name, xs in runs.items():
+        rec[name] = {"ms": spread([x[0] for x in xs]), "gathered_bytes": xs[0][1], "decode_launches": xs[0][2]}
+    rec["filtered_over_all"] = spread([f[0] / g[0] for f, g in zip(runs["filtered"], runs["all"])], 3)
+    emit(rec, a.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=65536)
@@ -258,6 +315,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--e2e-mib", type=int, default=100)
     ap.add_argument("--e2e-rounds", type=int, default=3)
+    ap.add_argument("--prune-groups", type=int, default=0,
+                    help="only the pruning phase: a file of this many row groups, a filter that keeps one")
     ap.add_argument("--out", default=None)
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu: a DRAM-tier cluster and the host loops (a dry run of the tool; variants do not apply)")
@@ -271,9 +330,12 @@ def main():
     C = lib()
     with cluster("2GB", a.device) as c:
         fs = c.client()
-        pass_phase(torch, C, fs, a)
-        if a.e2e_mib:
-            e2e_phase(torch, fs, a)
+        if a.prune_groups:
+            prune_phase(torch, C, fs, a)
+        else:
+            pass_phase(torch, C, fs, a)
+            if a.e2e_mib:
+                e2e_phase(torch, fs, a)
         fs.close()
 
 

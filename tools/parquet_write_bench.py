@@ -16,6 +16,11 @@ a seed, so they lie on the device as a training loop has them.  From one process
     ``pa.table``, ``pq.write_table(compression="none")`` and ``fs.write_file``, alternating, by the
     host clock (both end with the file complete in the cache).
 
+With ``--statistics`` the writer computes and writes min / max / null_count
+(``statistics=True``): (a) then times the encode with and without them, alternating inside a round,
+and reports the added time and the added launches (``csrc/parquet_stats.hip``) per row group; (c)
+writes with them.
+
 Before timing, the written file is compared with the source through ``pq.read_table``.  One JSON
 line per measurement goes to stdout and to ``--out``.  Needs a GPU: it fails without one."""
 import argparse
@@ -56,6 +61,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--statistics", action="store_true",
+                    help="write statistics; the encode phase alternates with and without them")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu: a DRAM-tier cluster, the host loops and the host clock (a dry run of the tool)")
     a = ap.parse_args()
@@ -92,6 +99,7 @@ def main():
     shapes = {"numeric": (numeric_table(pa, a.rows, 1), None, ()),
               "text": (string_table(pa, a.rows, 2), {"s": ("s", "text")}, ()),
               "category": (string_table(pa, a.rows, 2), {"s": ("s", "category")}, ("s",))}
+    kw = {"statistics": True} if a.statistics else {}   # left out otherwise: the tool also runs on a tree without them
     with cluster("2GB", a.device) as c:
         fs = c.client()
         for shape, (tbl, spec, cats) in shapes.items():
@@ -99,27 +107,29 @@ def main():
             pq.write_table(tbl, buf, compression="none", row_group_size=a.rows)
             fs.write_file(f"/bench/{shape}-src.parquet", buf.getvalue(), write_type="MUST_CACHE")
             cols = read_parquet_columns(fs, f"/bench/{shape}-src.parquet", spec, device=a.device)
-            write_parquet_columns(fs, f"/bench/{shape}-check.parquet", cols, write_type="MUST_CACHE")
+            write_parquet_columns(fs, f"/bench/{shape}-check.parquet", cols, write_type="MUST_CACHE", **kw)
             got = pq.read_table(io.BytesIO(fs.read_file(f"/bench/{shape}-check.parquet")))
             if not got.equals(tbl.cast(got.schema)):
                 raise SystemExit(f"{shape}: the written file differs from the source")
             wcols, dev = P._write_columns(cols, ())
             writer = P.ParquetWriter(fs, "/bench/unused", write_type="MUST_CACHE")
             launches = C.parquet_encode_launches()
-            g = P._measure_group(wcols, 0, a.rows, None, dev)
+            stats_launches = C.parquet_stats_launches() if a.statistics else 0
+            g = P._measure_group(wcols, 0, a.rows, None, dev, **kw)
             P._layout_group(g, "error", writer._dict_offsets)
             out_bytes = int(P._emit_group(g).numel())
             launches = C.parquet_encode_launches() - launches
+            stats_launches = C.parquet_stats_launches() - stats_launches if a.statistics else 0
             src = torch.randint(0, 256, (out_bytes,), dtype=torch.uint8, device=a.device)
             dst = torch.empty_like(src)
             stream = int(torch.cuda.current_stream().cuda_stream) if gpu else 0
             clock = Clock()
-            total, passes, roof = [], [], []
+            total, passes, roof, plain = [], [], [], []
             for r in range(a.warmup + a.rounds):
-                def encode():
+                def encode(kw=kw):
                     clock.start()
                     t0 = time.perf_counter()
-                    g = P._measure_group(wcols, 0, a.rows, None, dev)
+                    g = P._measure_group(wcols, 0, a.rows, None, dev, **kw)
                     t1 = time.perf_counter()
                     P._layout_group(g, "error", writer._dict_offsets)
                     t2 = time.perf_counter()
@@ -136,10 +146,15 @@ def main():
                         dst.copy_(src)
                     return clock.stop()
 
-                first, second = (encode, copy) if r % 2 == 0 else (copy, encode)
-                x, y = first(), second()
-                enc, cp = (x, y) if r % 2 == 0 else (y, x)
+                fns = [("encode", encode), ("copy", copy)]
+                if a.statistics:                        # the same encode without statistics, in the same rotation
+                    fns.append(("plain", lambda: encode({})))
+                k = r % len(fns)
+                got = {name: fn() for name, fn in fns[k:] + fns[:k]}
+                enc, cp = got["encode"], got["copy"]
                 if r >= a.warmup:
+                    if a.statistics:
+                        plain.append(got["plain"][0])
                     total.append(enc[0])
                     passes.append(enc[1])
                     roof.append(cp)
@@ -148,10 +163,13 @@ def main():
                    "encode_over_copy": spread([t / c_ for t, c_ in zip(total, roof)], 1)}
             for k in ("measure", "layout", "emit"):
                 rec[k] = spread([p[k] for p in passes])
+            if a.statistics:
+                rec.update(statistics=True, stats_launches=stats_launches, encode_without=spread(plain),
+                           added=spread([t - p for t, p in zip(total, plain)]))
             emit(rec, a.out)
 
             def ours():
-                write_parquet_columns(fs, "/bench/e2e-ours.parquet", cols, write_type="MUST_CACHE")
+                write_parquet_columns(fs, "/bench/e2e-ours.parquet", cols, write_type="MUST_CACHE", **kw)
                 fs.delete("/bench/e2e-ours.parquet")
 
             def host():
@@ -169,7 +187,8 @@ def main():
                     sync()
                     if r >= a.warmup:
                         acc.append(1e3 * (time.perf_counter() - t0))
-            emit({"phase": "e2e", "shape": shape, "rows": a.rows, "unit": "ms", "device_write": spread(t_ours),
+            emit({"phase": "e2e", "shape": shape, "rows": a.rows, "unit": "ms", "statistics": a.statistics,
+                  "device_write": spread(t_ours),
                   "host_pyarrow_write": spread(t_host), "host_over_device": spread([h / o for h, o in zip(t_host, t_ours)], 2)},
                  a.out)
         fs.close()
