@@ -1316,10 +1316,13 @@ PYBIND11_MODULE(_C, m) {
     return py::make_tuple(v, cap);
   });
   // ("fast" | "general", unroll, grid) of the most recent ring-read launch; grid 0: none yet
-  m.def("seq_read_last_launch", [] {
+  // detail: the same followed by (cursor from the arguments, page entries in the arguments)
+  m.def("seq_read_last_launch", [](bool detail) -> py::tuple {
     const SeqReadLaunch l = seq_read_last_launch();
+    if (detail)
+      return py::make_tuple(l.fast ? "fast" : "general", l.unroll, l.grid, l.cursor_inline != 0, l.pages_inline);
     return py::make_tuple(l.fast ? "fast" : "general", l.unroll, l.grid);
-  });
+  }, py::arg("detail") = false);
   m.def("set_ragged_gather_variant", &set_ragged_gather_variant, py::arg("variant"), py::arg("chunk_shift") = 0);
   m.def("ragged_gather_chunk_shift", &ragged_gather_chunk_shift);
   m.def("set_delim_index_variant", &set_delim_index_variant, py::arg("variant"), py::arg("tile_shift") = 0);

@@ -42,6 +42,7 @@ hipError_t launch_batched_copy(const CopySeg* segs, int nseg, uint64_t total_chu
 void set_copy_variant(int variant, unsigned grid_cap);
 void copy_variant(int* variant, unsigned* grid_cap);
 
+constexpr uint32_t kSeqInlinePages = 4;   // page-table entries a launch carries in its arguments
 // Device-cursor sequential multi-stream read (StressWorkerBench shape, K1 without per-read
 // descriptors).  S streams each issue `depth` consecutive read(buf) calls per launch over one
 // cached file whose pages are listed in `ftab` (file page -> arena page).  Stream s's call
@@ -67,11 +68,40 @@ struct SeqReadArgs {
   // launch_base % cycle, for the fast kernel (which never divides); the general kernel reduces
   // launch_base itself.  Left unset (>= cycle), the launch takes the general kernel.
   uint64_t base_mod = ~0ull;
+  // What the host already knows about the start of this launch, for the fast kernel alone, so that
+  // a wave's first data load does not wait for two dependent table loads (all zero: nothing known).
+  //   cursor_set: every c_init[s] equals c_uniform (< cycle); the kernel does not load c_init.
+  //   page_n:     page_tab[i] = ftab[(page_first + i) % file_pages] for i < page_n (<= kSeqInlinePages; entries below 2^32),
+  //               file_pages = ceil(file_len / page size): the pages from the launch's earliest
+  //               call on, page 0 following the file's last page as call 0 follows the EOF call.
+  uint64_t c_uniform = 0;
+  uint32_t cursor_set = 0;
+  uint32_t page_n = 0;
+  uint32_t page_first = 0;
+  uint32_t file_pages = 0;
+  uint32_t page_tab[kSeqInlinePages] = {};
 };
 constexpr uint32_t kSeqReadMaxStreams = 8192;
 // Two kernels (kernels.hip): the fast one when buf is a multiple of 1 KiB, the page size is at
-// least 1 KiB and base_mod is set; the general one for every other shape.
+// least 1 KiB, base_mod is set and the launch's and the file's 1 KiB chunks count below 2^32; the
+// general one for every other shape.
 hipError_t launch_seq_read(const SeqReadArgs& a, hipStream_t stream);
+// The same in two halves, for a caller that repeats one shape: plan_seq_read validates, picks the
+// kernel and (fast kernel) asks the current device for its persistent grid, once; launch_seq_plan
+// launches what was picked with this step's scalars and asks the runtime nothing.  A plan holds
+// while seq_read_epoch() stays what it was when the plan was made (set_seq_read_variant moves it)
+// and the shape (buf, depth, streams, page_shift, file_len, cycle, footprint) and device are the
+// plan's.
+struct SeqReadPlan {
+  const void* kernel = nullptr;   // fast instantiation; null: the general kernel, chosen per launch
+  uint32_t epoch = 0;             // 0: no plan yet
+  uint32_t grid = 0;
+  uint32_t cpr_shift = 0, depth_shift = 0;
+  int unroll = 0;
+};
+uint32_t seq_read_epoch();
+hipError_t plan_seq_read(const SeqReadArgs& a, SeqReadPlan* plan);
+hipError_t launch_seq_plan(const SeqReadPlan& plan, const SeqReadArgs& a, hipStream_t stream);
 // A/B switch for the sequential-read kernels (bit0: nontemporal ring stores, bit1: unroll 16 — in
 // the general kernel only where depth and buf / 16 are powers of two —, bit2: nontemporal loads;
 // -1: the launcher chooses by the launch's footprint).  grid_cap 0 keeps the cap; the fast kernel's
@@ -79,12 +109,14 @@ hipError_t launch_seq_read(const SeqReadArgs& a, hipStream_t stream);
 // they stand, so a caller can put them back.
 void set_seq_read_variant(int variant, unsigned grid_cap);
 void seq_read_variant(int* variant, unsigned* grid_cap);
-// What the most recent launch_seq_read in this process launched (fast = 0: the general kernel;
-// grid = 0: nothing yet).
+// What the most recent ring-read launch in this process launched (fast = 0: the general kernel;
+// grid = 0: nothing yet), and what it took from its arguments instead of from memory.
 struct SeqReadLaunch {
   int fast;
   int unroll;
   unsigned grid;
+  int cursor_inline;      // 1: the kernel took the shared cursor from the arguments
+  unsigned pages_inline;  // page-table entries the kernel could take from the arguments
 };
 SeqReadLaunch seq_read_last_launch();
 // Store-only roof of the ring read: `bytes` (a multiple of 16) at dst (16-byte aligned) are filled

@@ -147,10 +147,13 @@ hipError_t launch_batched_copy(const CopySeg* segs, int nseg, uint64_t total_chu
 // (grid = CUs x resident workgroups, capped by grid_cap).  Everything that decides addresses —
 // stream, call, call index c, EOF, the page lookup, the source and ring bases — is worked out from
 // wave-uniform values (blockIdx, the wave id through readfirstlane, kernel arguments), so it lives
-// in SGPRs and c_init[s] / ftab[page] come through scalar loads; a lane only adds lane * 16.  No
-// LDS, no barrier and no 64-bit modulo: the host passes launch_base % cycle and c_init[s] < cycle,
-// so c is two adds and two compare-subtracts; a launch with depth > cycle (several passes inside
-// one launch) runs a second instantiation of the loop that first reduces k by a 32-bit modulo.
+// in SGPRs and c_init[s] / ftab[page] come through scalar loads — or straight from the arguments
+// where the host sent them (the streams' shared cursor, the first pages of the launch's window:
+// SeqReadArgs); a lane only adds lane * 16.  Positions are counted in 1 KiB chunks, which the
+// launcher has checked to fit 32 bits.  No LDS, no barrier and no 64-bit modulo: the host passes
+// launch_base % cycle and c_init[s] < cycle, so c is two compare-subtracts; a launch with
+// depth > cycle (several passes inside one launch) runs a second instantiation of the loop that
+// first reduces k by a 32-bit modulo.
 // Consecutive chunks are consecutive calls of one stream, so a trip that stays inside one stream's
 // ring, one page and the file is contiguous in both: it is resolved once and issues its U 16-B
 // loads back to back, then its U stores.  Any other trip (a page or stream boundary, an EOF call,
@@ -228,32 +231,56 @@ __global__ __launch_bounds__(kSeqThreads) void seq_read_kernel(SeqReadArgs a, ui
 }
 
 // Stream, call and chunk-of-the-slot of chunk q (q < streams * depth * cpr), all wave-uniform.
+// The launcher admits a launch to the fast kernel only where its chunks, and the file's, count
+// below 2^32, so the fast kernel's index math is 32-bit scalar work throughout.
 template <bool POW2>
-__device__ __forceinline__ void seq_split(const SeqReadArgs& a, uint64_t q, uint64_t cpr, uint32_t cpr_shift,
-                                          uint32_t depth_shift, uint32_t* s, uint32_t* k, uint64_t* ci) {
+__device__ __forceinline__ void seq_split(const SeqReadArgs& a, uint32_t q, uint32_t cpr, uint32_t cpr_shift,
+                                          uint32_t depth_shift, uint32_t* s, uint32_t* k, uint32_t* ci) {
   if constexpr (POW2) {
-    const uint64_t rd = q >> cpr_shift;
+    const uint32_t rd = q >> cpr_shift;
     *ci = q & (cpr - 1);
-    *s = (uint32_t)(rd >> depth_shift);
-    *k = (uint32_t)(rd & (a.depth - 1));
+    *s = rd >> depth_shift;
+    *k = rd & (a.depth - 1);
   } else {
-    const uint64_t rd = q / cpr;
+    const uint32_t rd = q / cpr;
     *ci = q - rd * cpr;
-    *s = (uint32_t)(rd / a.depth);
-    *k = (uint32_t)(rd - (uint64_t)*s * a.depth);
+    *s = rd / a.depth;
+    *k = rd - *s * a.depth;
   }
 }
 
-// Call index of a stream's k-th call of this launch, c0 = c_init[s]: c0, base_mod and (after the
-// MULTI reduction) k are all below cycle, so two compare-subtracts do.  MULTI: depth > cycle, a
-// launch holds several passes and k needs a real (32-bit, wave-uniform) modulo first.
+// First call index of this launch for a stream whose cursor is c0: (c0 + base_mod) % cycle.  Both
+// are below cycle, so one compare-subtract does; comparing before adding keeps it inside 32 bits.
+__device__ __forceinline__ uint32_t seq_first_call(const SeqReadArgs& a, uint32_t c0) {
+  const uint32_t room = a.cycle - (uint32_t)a.base_mod;   // > 0
+  return c0 >= room ? c0 - room : c0 + (uint32_t)a.base_mod;
+}
+
+// Call index of the k-th call after `first` (< cycle).  MULTI: depth > cycle, a launch holds
+// several passes and k needs a real (32-bit, wave-uniform) modulo first.
 template <bool MULTI>
-__device__ __forceinline__ uint64_t seq_call_index(const SeqReadArgs& a, uint64_t c0, uint32_t k) {
+__device__ __forceinline__ uint32_t seq_call_index(const SeqReadArgs& a, uint32_t first, uint32_t k) {
   if constexpr (MULTI) k %= a.cycle;
-  uint64_t c = c0 + a.base_mod;
-  c = c >= a.cycle ? c - a.cycle : c;
-  c += k;
-  return c >= a.cycle ? c - a.cycle : c;
+  const uint32_t room = a.cycle - first;                  // > 0
+  return k >= room ? k - room : first + k;
+}
+
+// ftab[page], from the arguments where the launch carries it (SeqReadArgs::page_tab: the pages
+// from page_first on, wrapping to page 0 behind the file's last page): a few scalar selects
+// instead of a load that the first data load of a wave would have to wait for.  The entries are
+// read into scalar registers once, at the loop's top, and pinned there: left to itself the compiler
+// selects between the ADDRESSES of the entries and of ftab[page] and issues one vector load for
+// both.  The host sends entries only where they fit 32 bits, so they take four registers.
+__device__ __forceinline__ uint64_t seq_page(const SeqReadArgs& a, uint32_t e0, uint32_t e1, uint32_t e2, uint32_t e3,
+                                             const int64_t* __restrict__ ftab, uint32_t page) {
+  static_assert(kSeqInlinePages == 4, "one register and one select per inline entry");
+  const uint32_t d = page >= a.page_first ? page - a.page_first : page + (a.file_pages - a.page_first);
+  if (d >= a.page_n) return (uint64_t)ftab[page];
+  uint32_t e = e0;
+  e = d == 1 ? e1 : e;
+  e = d == 2 ? e2 : e;
+  e = d == 3 ? e3 : e;
+  return e;
 }
 
 // The body of the fast kernel (the kernel picks MULTI once, at its top).  A trip owns the U
@@ -261,39 +288,51 @@ __device__ __forceinline__ uint64_t seq_call_index(const SeqReadArgs& a, uint64_
 // ring, before the file's end (so none is an EOF call) and in one page, file and ring are both
 // contiguous over the trip: one page lookup, and the U loads and U stores differ by u KiB.  Any
 // other trip — a page or stream boundary inside it, an EOF call, the end of a pass or of the index
-// space — resolves every chunk by itself, four at a time, in straight-line stages so that the
-// scalar loads of a stage go out together and the four data loads follow each other before the
-// four stores: n[u] = bytes to move, 1024, the tail of a pass, or 0; a chunk that moves nothing
+// space — resolves every chunk by itself, two at a time (four held scalar registers that the
+// contiguous trips' page entries need), in straight-line stages so that the scalar loads of a stage
+// go out together and the data loads follow each other before the stores; it always takes
+// ftab[page] from the table: n[u] = bytes to move, 1024, the tail of a pass, or 0; a chunk that moves nothing
 // looks up stream 0 / page 0, so every load stays inside its table.  Lanes wholly before n[u] use
 // the vector, the lane that holds the end finishes the tail bytes.
+//
+// A stream's cursor comes from the arguments where all streams share it (cursor_set) and from
+// c_init[s] otherwise; with the page entries in the arguments too (seq_page), the first data load
+// of a lockstep wave waits for the kernel-argument load alone.  File positions are counted in
+// 1 KiB chunks (f = c * cpr + ci): 32-bit, like everything else that decides an address.
 template <bool POW2, int U, int SP, int LP, bool MULTI>
 __device__ __forceinline__ void seq_fast_loop(const SeqReadArgs& a, const uint8_t* __restrict__ arena,
                                               const int64_t* __restrict__ ftab,
                                               const uint64_t* __restrict__ c_init, uint8_t* __restrict__ dst,
                                               uint32_t cpr_shift, uint32_t depth_shift) {
   constexpr uint32_t kWaves = kSeqThreads / 64;
-  constexpr uint64_t kTrip = (uint64_t)U * kSeqChunk;
-  constexpr int kGen = 4;                                // chunks per batch of the general path
+  constexpr int kGen = 2;                                // chunks per batch of the general path
   const uint32_t lane16 = (threadIdx.x & 63u) * 16u;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint64_t cpr = a.buf >> kSeqChunkShift;          // chunks per read slot
-  const uint64_t per_stream = (uint64_t)a.depth * cpr;
-  const uint64_t nchunks = (uint64_t)a.streams * per_stream;
-  const uint64_t ngroups = (nchunks + U - 1) / U;        // U is a power of two: a shift
-  const uint64_t nwaves = (uint64_t)gridDim.x * kWaves;
-  const uint64_t pmask = (1ull << a.page_shift) - 1;
-  for (uint64_t g = (uint64_t)blockIdx.x * kWaves + wave; g < ngroups; g += nwaves) {
-    uint32_t s0, k0;
-    uint64_t ci0;
+  const uint32_t cpr = (uint32_t)(a.buf >> kSeqChunkShift);          // chunks per read slot
+  const uint32_t per_stream = a.depth * cpr;
+  const uint32_t nchunks = a.streams * per_stream;
+  const uint32_t ngroups = (nchunks + U - 1) / U;        // U is a power of two: a shift
+  const uint32_t nwaves = gridDim.x * kWaves;
+  const uint32_t file_chunks = (uint32_t)(a.file_len >> kSeqChunkShift);   // whole chunks of the file
+  const uint32_t pc_shift = a.page_shift - kSeqChunkShift;           // chunks per page
+  const uint32_t pcmask = (1u << pc_shift) - 1;
+  const uint32_t first_shared = seq_first_call(a, (uint32_t)a.c_uniform);
+  uint32_t e0 = a.page_tab[0], e1 = a.page_tab[1], e2 = a.page_tab[2], e3 = a.page_tab[3];
+  asm volatile("" : "+s"(e0), "+s"(e1), "+s"(e2), "+s"(e3));   // see seq_page
+  for (uint32_t g = blockIdx.x * kWaves + wave; g < ngroups; g += nwaves) {
+    uint32_t s0, k0, ci0;
     seq_split<POW2>(a, g * U, cpr, cpr_shift, depth_shift, &s0, &k0, &ci0);
-    const uint64_t w0 = (uint64_t)k0 * cpr + ci0;        // chunk of the stream's ring
-    const uint64_t off0 = seq_call_index<MULTI>(a, c_init[s0], k0) * a.buf + (ci0 << kSeqChunkShift);
-    u32x4 v[U];
+    const uint32_t w0 = k0 * cpr + ci0;                  // chunk of the stream's ring
+    const uint32_t first = a.cursor_set ? first_shared : seq_first_call(a, (uint32_t)c_init[s0]);
+    const uint32_t f0 = seq_call_index<MULTI>(a, first, k0) * cpr + ci0;   // chunk of the file
     // the EOF call starts at or past file_len, so the second test also says "no EOF call inside"
-    if (w0 + U <= per_stream && off0 + kTrip <= a.file_len && (off0 & pmask) + kTrip <= pmask + 1) {
-      const uint64_t page = (uint64_t)ftab[off0 >> a.page_shift];
-      const u32x4* sp = reinterpret_cast<const u32x4*>(arena + (page << a.page_shift) + (off0 & pmask) + lane16);
-      u32x4* dp = reinterpret_cast<u32x4*>(dst + (uint64_t)s0 * a.stream_stride + (w0 << kSeqChunkShift) + lane16);
+    if (w0 + U <= per_stream && f0 + U <= file_chunks && (f0 & pcmask) + U <= pcmask + 1) {
+      const uint64_t page = seq_page(a, e0, e1, e2, e3, ftab, f0 >> pc_shift);
+      const u32x4* sp = reinterpret_cast<const u32x4*>(
+          arena + (page << a.page_shift) + ((uint64_t)(f0 & pcmask) << kSeqChunkShift) + lane16);
+      u32x4* dp = reinterpret_cast<u32x4*>(dst + (uint64_t)s0 * a.stream_stride +
+                                           ((uint64_t)w0 << kSeqChunkShift) + lane16);
+      u32x4 v[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) v[u] = ld16<LP>(sp + u * (kSeqChunk / 16));
 #pragma unroll
@@ -303,40 +342,40 @@ __device__ __forceinline__ void seq_fast_loop(const SeqReadArgs& a, const uint8_
     // not unrolled: kGen chunks at a time keep this rare path's registers below the hot path's
 #pragma unroll 1
     for (int h = 0; h < U; h += kGen) {
-      uint64_t dof[kGen], c0[kGen], sof[kGen];
-      uint32_t k[kGen], n[kGen];
-      int64_t page[kGen];
+      uint64_t dof[kGen], sof[kGen];
+      uint32_t c0[kGen], k[kGen], ci[kGen], n[kGen];
+      uint64_t page[kGen];
+      u32x4 w[kGen] = {};                                // this batch's own: nothing is carried between batches
 #pragma unroll
       for (int u = 0; u < kGen; ++u) {                   // stream, call, ring offset, c_init[s]
-        const uint64_t q = g * U + h + u;
+        const uint32_t q = g * U + h + u;
         n[u] = q < nchunks ? kSeqChunk : 0;
         uint32_t s;
-        uint64_t ci;
-        seq_split<POW2>(a, q < nchunks ? q : 0, cpr, cpr_shift, depth_shift, &s, &k[u], &ci);
-        sof[u] = ci << kSeqChunkShift;
-        dof[u] = (uint64_t)s * a.stream_stride + (uint64_t)k[u] * a.buf + sof[u];
-        c0[u] = c_init[s];
+        seq_split<POW2>(a, q < nchunks ? q : 0, cpr, cpr_shift, depth_shift, &s, &k[u], &ci[u]);
+        dof[u] = (uint64_t)s * a.stream_stride + ((uint64_t)(k[u] * cpr + ci[u]) << kSeqChunkShift);
+        c0[u] = a.cursor_set ? (uint32_t)a.c_uniform : (uint32_t)c_init[s];
       }
 #pragma unroll
       for (int u = 0; u < kGen; ++u) {                   // call index, file offset, bytes, ftab[page]
-        const uint64_t c = seq_call_index<MULTI>(a, c0[u], k[u]);
-        const uint64_t off = c * a.buf + sof[u];
+        const uint32_t c = seq_call_index<MULTI>(a, seq_first_call(a, c0[u]), k[u]);
+        const uint32_t f = c * cpr + ci[u];
+        const uint64_t off = (uint64_t)f << kSeqChunkShift;
         const bool data = c != a.cycle - 1 && off < a.file_len;   // not the EOF call, not past the end
         const uint64_t left = data ? a.file_len - off : 0;
         n[u] = left < n[u] ? (uint32_t)left : n[u];
         sof[u] = data ? off : 0;
-        page[u] = ftab[sof[u] >> a.page_shift];
+        page[u] = (uint64_t)ftab[sof[u] >> a.page_shift];   // this rare path keeps to the table: fewer live registers
       }
 #pragma unroll
       for (int u = 0; u < kGen; ++u) {                   // source address; the loads, back to back
-        const uint8_t* src = arena + ((uint64_t)page[u] << a.page_shift) + (sof[u] & pmask);
+        const uint8_t* src = arena + (page[u] << a.page_shift) + (sof[u] & ((1ull << a.page_shift) - 1));
         sof[u] = reinterpret_cast<uint64_t>(src);
-        if (lane16 + 16 <= n[u]) v[u] = ld16<LP>(reinterpret_cast<const u32x4*>(src + lane16));
+        if (lane16 + 16 <= n[u]) w[u] = ld16<LP>(reinterpret_cast<const u32x4*>(src + lane16));
       }
 #pragma unroll
       for (int u = 0; u < kGen; ++u) {
         if (lane16 + 16 <= n[u]) {
-          st16<SP>(reinterpret_cast<u32x4*>(dst + dof[u] + lane16), v[u]);
+          st16<SP>(reinterpret_cast<u32x4*>(dst + dof[u] + lane16), w[u]);
         } else if (lane16 < n[u]) {
           // the lane that holds the end of the pass: its tail bytes (same page, a chunk does not straddle)
           const uint8_t* src = reinterpret_cast<const uint8_t*>(sof[u]);
@@ -367,16 +406,20 @@ __global__ __launch_bounds__(kSeqThreads) void seq_read_fast_kernel(
 static int g_seq_variant = -1;
 static unsigned g_seq_grid_cap = 8192;
 
+static uint32_t g_seq_epoch = 1;   // moves with every set_seq_read_variant: plans made before it are stale
+
 void set_seq_read_variant(int variant, unsigned grid_cap) {
   g_seq_variant = variant;
   if (grid_cap) g_seq_grid_cap = grid_cap;
+  if (++g_seq_epoch == 0) g_seq_epoch = 1;
 }
 void seq_read_variant(int* variant, unsigned* grid_cap) {
   *variant = g_seq_variant;
   *grid_cap = g_seq_grid_cap;
 }
+uint32_t seq_read_epoch() { return g_seq_epoch; }
 
-static SeqReadLaunch g_seq_last;   // what the last launch_seq_read chose (all zero: none yet)
+static SeqReadLaunch g_seq_last;   // what the last ring-read launch chose (all zero: none yet)
 
 SeqReadLaunch seq_read_last_launch() { return g_seq_last; }
 
@@ -410,16 +453,15 @@ static hipError_t resident_workgroups(K kernel, unsigned (&cached)[kMaxDev], uns
   return hipSuccess;
 }
 
-template <bool P2, int U, int SP, int LP>
-static hipError_t seq_fast_resident(unsigned* out) {
-  static unsigned cached[kMaxDev] = {};
-  return resident_workgroups(seq_read_fast_kernel<P2, U, SP, LP>, cached, out);
-}
+using SeqFastKernel = void (*)(SeqReadArgs, const uint8_t*, const int64_t*, const uint64_t*, uint8_t*, uint32_t,
+                               uint32_t);
 
+// The plan of one fast instantiation: the kernel, its persistent grid (capped) and the two shifts.
 template <bool P2, int U, int SP, int LP>
-static hipError_t launch_seq_fast(const SeqReadArgs& a, hipStream_t stream) {
+static hipError_t plan_seq_fast(const SeqReadArgs& a, SeqReadPlan* plan) {
+  static unsigned cached[kMaxDev] = {};
   unsigned resident = 0;
-  const hipError_t e = seq_fast_resident<P2, U, SP, LP>(&resident);
+  const hipError_t e = resident_workgroups(seq_read_fast_kernel<P2, U, SP, LP>, cached, &resident);
   if (e != hipSuccess) return e;
   const uint64_t cpr = a.buf >> kSeqChunkShift;
   const uint64_t nchunks = (uint64_t)a.streams * a.depth * cpr;
@@ -429,38 +471,86 @@ static hipError_t launch_seq_fast(const SeqReadArgs& a, hipStream_t stream) {
   if (blocks > resident) blocks = resident;
   if (blocks > g_seq_grid_cap) blocks = g_seq_grid_cap;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((seq_read_fast_kernel<P2, U, SP, LP>), dim3((unsigned)blocks), dim3(kSeqThreads), 0, stream,
-                     a, a.arena, a.ftab, a.c_init, a.dst, log2u(cpr), log2u(a.depth));
-  g_seq_last = SeqReadLaunch{1, U, (unsigned)blocks};
+  plan->kernel = reinterpret_cast<const void*>(static_cast<SeqFastKernel>(seq_read_fast_kernel<P2, U, SP, LP>));
+  plan->grid = (uint32_t)blocks;
+  plan->cpr_shift = log2u(cpr);
+  plan->depth_shift = log2u(a.depth);
+  plan->unroll = U;
+  return hipSuccess;
+}
+
+static bool seq_args_ok(const SeqReadArgs& a) {
+  return !(a.streams > kSeqReadMaxStreams || (a.buf & 15) || (a.stream_stride & 15) || ((uint64_t)a.dst & 15) ||
+           ((uint64_t)a.arena & 15));
+}
+static bool seq_args_empty(const SeqReadArgs& a) {
+  return a.streams == 0 || a.depth == 0 || a.buf == 0 || a.file_len == 0;
+}
+static int seq_variant_of(const SeqReadArgs& a) {
+  const uint64_t fp = a.footprint ? a.footprint : a.file_len;
+  return g_seq_variant >= 0 ? g_seq_variant : (fp >= (128ull << 20) ? 4 : 0);
+}
+
+// Whole 1 KiB chunks that never straddle a page, the reduced launch base the kernel's
+// compare-subtracts rely on, and chunk counts (of the launch and of the file's calls, with room for
+// one trip) that fit the kernel's 32-bit index math.  Everything else takes the general kernel.
+static bool seq_fast_shape(const SeqReadArgs& a) {
+  if ((a.buf & (kSeqChunk - 1)) || a.page_shift < kSeqChunkShift || a.page_shift > 40 || a.base_mod >= a.cycle)
+    return false;
+  const uint64_t cpr = a.buf >> kSeqChunkShift, lim = (1ull << 32) - 16;
+  if (cpr >= (1ull << 31)) return false;
+  const uint64_t per_stream = (uint64_t)a.depth * cpr;
+  return per_stream < lim && (uint64_t)a.streams * per_stream < lim && (uint64_t)a.cycle * cpr < lim;
+}
+
+hipError_t plan_seq_read(const SeqReadArgs& a, SeqReadPlan* plan) {
+  *plan = SeqReadPlan{};
+  plan->epoch = g_seq_epoch;
+  if (seq_args_empty(a)) return hipSuccess;
+  if (!seq_args_ok(a)) return hipErrorInvalidValue;
+  if (!seq_fast_shape(a)) return hipSuccess;             // the general kernel: nothing to keep
+  const int var = seq_variant_of(a);
+  const bool p2 = is_pow2(a.buf >> kSeqChunkShift) && is_pow2(a.depth);
+  const int sel = (p2 ? 8 : 0) | ((var & 2) ? 4 : 0) | ((var & 1) ? 2 : 0) | ((var & 4) ? 1 : 0);
+  switch (sel) {
+#define AMDX_FAST(N, P2, U, SP, LP) case N: return plan_seq_fast<P2, U, SP, LP>(a, plan)
+    AMDX_FAST(0, false, 8, 0, 0); AMDX_FAST(1, false, 8, 0, 1); AMDX_FAST(2, false, 8, 1, 0);
+    AMDX_FAST(3, false, 8, 1, 1); AMDX_FAST(4, false, 16, 0, 0); AMDX_FAST(5, false, 16, 0, 1);
+    AMDX_FAST(6, false, 16, 1, 0); AMDX_FAST(7, false, 16, 1, 1); AMDX_FAST(8, true, 8, 0, 0);
+    AMDX_FAST(9, true, 8, 0, 1); AMDX_FAST(10, true, 8, 1, 0); AMDX_FAST(11, true, 8, 1, 1);
+    AMDX_FAST(12, true, 16, 0, 0); AMDX_FAST(13, true, 16, 0, 1); AMDX_FAST(14, true, 16, 1, 0);
+    default: AMDX_FAST(15, true, 16, 1, 1);
+#undef AMDX_FAST
+  }
+}
+
+static hipError_t launch_seq_general(const SeqReadArgs& a, hipStream_t stream);
+
+hipError_t launch_seq_plan(const SeqReadPlan& plan, const SeqReadArgs& a, hipStream_t stream) {
+  if (seq_args_empty(a)) return hipSuccess;
+  if (!plan.kernel) return seq_args_ok(a) ? launch_seq_general(a, stream) : hipErrorInvalidValue;
+  // what the kernel takes on trust from the arguments must be inside its tables
+  if (a.base_mod >= a.cycle || a.page_n > kSeqInlinePages || (a.cursor_set && a.c_uniform >= a.cycle) ||
+      (a.page_n && (a.file_pages == 0 || a.page_first >= a.file_pages)))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(reinterpret_cast<SeqFastKernel>(const_cast<void*>(plan.kernel)), dim3(plan.grid),
+                     dim3(kSeqThreads), 0, stream, a, a.arena, a.ftab, a.c_init, a.dst, plan.cpr_shift,
+                     plan.depth_shift);
+  g_seq_last = SeqReadLaunch{1, plan.unroll, plan.grid, a.cursor_set ? 1 : 0, a.page_n};
   return hipGetLastError();
 }
 
 hipError_t launch_seq_read(const SeqReadArgs& a, hipStream_t stream) {
-  if (a.streams == 0 || a.depth == 0 || a.buf == 0 || a.file_len == 0) return hipSuccess;
-  if (a.streams > kSeqReadMaxStreams || (a.buf & 15) || (a.stream_stride & 15) ||
-      ((uint64_t)a.dst & 15) || ((uint64_t)a.arena & 15))
-    return hipErrorInvalidValue;
+  SeqReadPlan plan;
+  const hipError_t e = plan_seq_read(a, &plan);
+  return e != hipSuccess ? e : launch_seq_plan(plan, a, stream);
+}
+
+static hipError_t launch_seq_general(const SeqReadArgs& a, hipStream_t stream) {
   const uint64_t vpr = a.buf >> 4;
   const uint64_t nvec = (uint64_t)a.streams * a.depth * vpr;
-  const uint64_t fp = a.footprint ? a.footprint : a.file_len;
-  const int var = g_seq_variant >= 0 ? g_seq_variant : (fp >= (128ull << 20) ? 4 : 0);
+  const int var = seq_variant_of(a);
   const int unroll = (var & 2) ? 16 : 8;
-  // Fast path: whole 1 KiB chunks that never straddle a page, and the reduced launch base the
-  // kernel's compare-subtracts rely on.  Everything else takes the general kernel below.
-  if ((a.buf & (kSeqChunk - 1)) == 0 && a.page_shift >= kSeqChunkShift && a.base_mod < a.cycle) {
-    const bool p2 = is_pow2(a.buf >> kSeqChunkShift) && is_pow2(a.depth);
-    const int sel = (p2 ? 8 : 0) | (unroll == 16 ? 4 : 0) | ((var & 1) ? 2 : 0) | ((var & 4) ? 1 : 0);
-    switch (sel) {
-#define AMDX_FAST(N, P2, U, SP, LP) case N: return launch_seq_fast<P2, U, SP, LP>(a, stream)
-      AMDX_FAST(0, false, 8, 0, 0); AMDX_FAST(1, false, 8, 0, 1); AMDX_FAST(2, false, 8, 1, 0);
-      AMDX_FAST(3, false, 8, 1, 1); AMDX_FAST(4, false, 16, 0, 0); AMDX_FAST(5, false, 16, 0, 1);
-      AMDX_FAST(6, false, 16, 1, 0); AMDX_FAST(7, false, 16, 1, 1); AMDX_FAST(8, true, 8, 0, 0);
-      AMDX_FAST(9, true, 8, 0, 1); AMDX_FAST(10, true, 8, 1, 0); AMDX_FAST(11, true, 8, 1, 1);
-      AMDX_FAST(12, true, 16, 0, 0); AMDX_FAST(13, true, 16, 0, 1); AMDX_FAST(14, true, 16, 1, 0);
-      default: AMDX_FAST(15, true, 16, 1, 1);
-#undef AMDX_FAST
-    }
-  }
   uint64_t blocks = (nvec + (uint64_t)kSeqThreads * unroll - 1) / ((uint64_t)kSeqThreads * unroll);
   if (blocks > g_seq_grid_cap) blocks = g_seq_grid_cap;
   if (blocks < 1) blocks = 1;
@@ -484,7 +574,7 @@ hipError_t launch_seq_read(const SeqReadArgs& a, hipStream_t stream) {
     else { if (sp) AMDX_SEQ(false, 8, 1, 0); else AMDX_SEQ(false, 8, 0, 0); }
   }
 #undef AMDX_SEQ
-  g_seq_last = SeqReadLaunch{0, p2 ? unroll : 8, (unsigned)blocks};
+  g_seq_last = SeqReadLaunch{0, p2 ? unroll : 8, (unsigned)blocks, 0, 0};
   return hipGetLastError();
 }
 

@@ -66,6 +66,14 @@ void RingReadSession::finish_init(const std::vector<uint64_t>& start_offsets) {
   const uint64_t distinct = (uint64_t)(std::unique(starts.begin(), starts.end()) - starts.begin());
   footprint_ = std::min<uint64_t>(file_len_, distinct * depth_ * buf_);
   lockstep_ = distinct == 1;
+  // page entries a launch carries in its arguments: only where page numbers and entries fit 32 bits
+  const uint64_t pages = (file_len_ + (1ull << view_.page_shift) - 1) >> view_.page_shift;
+  bool fit = pages < (1ull << 32) && pages <= view_.vtab.size();
+  for (uint64_t p = 0; fit && p < pages; ++p) fit = view_.vtab[p] >= 0 && view_.vtab[p] < (int64_t)(1ull << 32);
+  if (fit) {
+    file_pages_ = (uint32_t)pages;
+    inline_pages_ = kSeqInlinePages;
+  }
   if (on_device_) {
     if (buf_ & 15 || stride_ & 15 || dst_ & 15)
       throw StoreError(kErrInvalidArgument, "ring read: buffer size, stride and ring base must be 16-byte aligned");
@@ -124,8 +132,25 @@ uint64_t RingReadSession::step(uint64_t stream, uint64_t* eofs) {
     a.depth = depth_;
     a.page_shift = view_.page_shift;
     a.footprint = footprint_;
+    // what the kernel would otherwise look up before its first load: the shared cursor, and the
+    // page entries from the launch's earliest call on (stream 0's where the cursors differ); after
+    // the file's last page comes page 0, as call 0 follows the EOF call
+    a.cursor_set = lockstep_;
+    a.c_uniform = c_init_[0];
+    uint64_t first = c_init_[0] + base_mod_;
+    if (first >= cycle_) first -= cycle_;
+    uint64_t page = first == cycle_ - 1 ? 0 : (first * buf_) >> view_.page_shift;
+    a.page_first = (uint32_t)page;
+    a.file_pages = file_pages_;
+    a.page_n = inline_pages_;
+    for (uint32_t i = 0; i < inline_pages_; ++i) {
+      a.page_tab[i] = (uint32_t)view_.vtab[page];
+      if (++page == file_pages_) page = 0;
+    }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    AMDX_HIP(launch_seq_read(a, st));
+    // kernel, persistent grid and shifts are the session's until the variant is set anew
+    if (plan_.epoch != seq_read_epoch()) AMDX_HIP(plan_seq_read(a, &plan_));
+    AMDX_HIP(launch_seq_plan(plan_, a, st));
     if (kind_ == (int)MemKind::kHost) AMDX_HIP(hipStreamSynchronize(st));
   } else {
     // CPU-only build/test path: same schedule with memcpy from the host arena

@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "kernels.h"
 #include "paged_view.h"
 
 namespace amdx {
@@ -63,6 +64,8 @@ class RingReadSession {
   bool lockstep_ = false;    // every stream starts at the same call: one accounting serves all
   uint32_t full_passes_ = 0, rem_calls_ = 0;   // depth / cycle, depth % cycle
   uint64_t base_mod_ = 0;    // calls_per_stream_ % cycle, carried from step to step
+  uint32_t file_pages_ = 0, inline_pages_ = 0;   // pages of the file; entries a launch carries (0: none)
+  SeqReadPlan plan_;         // kernel and grid of this session's launches (see plan_seq_read)
   DevBuf d_ftab_, d_cinit_;
   uint64_t calls_per_stream_ = 0, total_ = 0, reopens_ = 0;
   bool closed_ = false;
