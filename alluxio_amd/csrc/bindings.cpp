@@ -875,6 +875,17 @@ PYBIND11_MODULE(_C, m) {
         },
         py::arg("blob"), py::arg("blob_bytes"), py::arg("segs"), py::arg("nsegs"), py::arg("out"), py::arg("out_bytes"),
         py::arg("device"), py::arg("stream") = 0);
+  m.def("parquet_encode_lz4_raw",
+        [](int mode, uint64_t src, uint64_t src_bytes, uint64_t pages, uint64_t npages, uint64_t segs, uint64_t nsegs,
+           uint64_t scratch, uint64_t scratch_bytes, uint64_t result, uint64_t dst, uint64_t out, uint64_t out_bytes,
+           uint32_t warm, uint32_t segment, int device, uint64_t stream) {
+          py::gil_scoped_release rel;
+          parquet_encode_lz4_raw(mode, src, src_bytes, pages, npages, segs, nsegs, scratch, scratch_bytes, result, dst,
+                                 out, out_bytes, warm, segment, device, stream);
+        },
+        py::arg("mode"), py::arg("src"), py::arg("src_bytes"), py::arg("pages"), py::arg("npages"), py::arg("segs"),
+        py::arg("nsegs"), py::arg("scratch"), py::arg("scratch_bytes"), py::arg("result"), py::arg("dst"), py::arg("out"),
+        py::arg("out_bytes"), py::arg("warm"), py::arg("segment"), py::arg("device"), py::arg("stream") = 0);
   m.def("parquet_encode_launches", &parquet_encode_launches);
 
   // ---- Parquet column statistics (parquet_stats.cpp) --------------------------------------------

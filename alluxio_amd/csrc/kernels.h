@@ -14,6 +14,7 @@
 #include "field_parse_host.h"
 #include "json_fields_host.h"
 #include "json_text_host.h"
+#include "lz4_block_host.h"
 #include "parquet_encode_host.h"
 #include "parquet_host.h"
 #include "parquet_stats_host.h"
@@ -359,6 +360,15 @@ void set_lz4_encode_variant(int v);
 // the chunk does not fit dst_capacity (caller then stores it raw).
 hipError_t launch_lz4_compress(const Lz4Chunk* chunks, int n, int32_t* out_sizes,
                                hipStream_t stream);
+// One LZ4 block per page body of any size below 2^31 (lz4_block_host.h has the tables and the
+// rules): parse (one wave per segment row, sequences and records into scratch), link (one lane per
+// page: the places of the segments and the sizes into `result`) and merge (one workgroup per
+// segment row, blocks written at out + dst[page]).  Three launches whatever the pages; rows that do
+// not fit their buffers are skipped and flagged in `result`.  Null arrays, counts of zero or above
+// 2^31 and a scratch buffer shorter than its records are refused with hipErrorInvalidValue.
+hipError_t launch_lz4_page_parse(const LbArgs& a, hipStream_t stream);
+hipError_t launch_lz4_page_link(const LbArgs& a, hipStream_t stream);
+hipError_t launch_lz4_page_merge(const LbArgs& a, hipStream_t stream);
 
 // ---- device-resident annotations + grid-wide select (evict_alloc.hip) ----------------------
 // Slot-indexed arrays in HBM.  dir[s] = storage dir of a committed, statically evictable block

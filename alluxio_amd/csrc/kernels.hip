@@ -3184,6 +3184,196 @@ hipError_t launch_lz4_compress(const Lz4Chunk* chunks, int n, int32_t* out_sizes
   return hipGetLastError();
 }
 
+// One LZ4 block per page body of any size below 2^31 (Parquet LZ4_RAW pages): the segmented scheme
+// above without its limits.  The rules, the link and the merge plan are those of lz4_block_host.h.
+// Segments of a fixed size come from a host-built table, so one wave parses one segment of any page
+// with the 8 KiB table holding positions relative to `begin - warm`; the link is a pass of its own
+// (one lane per page), and the merge runs one workgroup per segment instead of one per chunk.  The
+// batch parse is a second copy of the loop of lz4_seg_parse_kernel, which stays as it was: 32-bit
+// page positions against a table base, the block's end rules bind every segment near the end, and
+// the segment and its warm-up bytes are staged in LDS (a page has few segments, so a wave's chain of
+// dependent loads, not occupancy, sets the time).
+__global__ __launch_bounds__(kLzThreads) void lz4_page_parse_kernel(const LbArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  uint16_t* table = reinterpret_cast<uint16_t*>(smem);                     // 8 KiB
+  uint8_t* stage = smem + (sizeof(uint16_t) << kLzHashLog);                // segment + warm bytes
+  const int lane = threadIdx.x;
+  uint32_t* recs = lb_recs(a);
+  for (uint64_t t = blockIdx.x; t < a.nsegs; t += gridDim.x) {
+    const int64_t* sg = a.segs + t * kLbSegCols;
+    uint32_t* rec = recs + t * kLbRecCols;
+    if (!lb_seg_ok(a, sg)) {                            // uniform: the whole wave skips the row
+      if (lane == 0) {
+        rec[kLbRecFirst] = kLbNone;
+        rec[kLbRecCode] = rec[kLbRecTail] = 0;
+        rec[kLbRecBytes] = kLbNone;
+      }
+      continue;
+    }
+    const uint8_t* __restrict__ gsrc = a.src + sg[kLbSegSrc];
+    const uint32_t len = (uint32_t)a.pages[(uint64_t)sg[kLbSegPage] * kLbPageCols + kLbPageLen];
+    const uint32_t sb = (uint32_t)sg[kLbSegBegin], se = (uint32_t)sg[kLbSegEnd];
+    const uint32_t base = sb > a.warm ? sb - a.warm : 0;
+    uint8_t* __restrict__ dst = a.scratch + sg[kLbSegScratch];
+    const uint32_t seg_cap = (uint32_t)lb_bound(se - sb);
+    // body bytes [base, se) into LDS: every read below lies in them (a probe reads 4 bytes before
+    // se, a match ends by se, literals start at or after sb); src[p - base] is body byte p
+    for (uint32_t i = lane; i < se - base; i += kLzThreads) stage[i] = gsrc[base + i];
+    const uint8_t* src = stage;
+    for (uint32_t i = lane; i < (1u << kLzHashLog); i += kLzThreads) table[i] = 0xFFFF;
+    __syncthreads();
+    for (uint32_t p = base + lane; p < sb; p += kLzThreads)
+      if (p + 4 <= se) table[lz_hash(lzb_read32<true>(src + (p - base)))] = (uint16_t)(p - base);
+    __syncthreads();
+    uint32_t match_limit, end_match;
+    lb_limits(len, se, &match_limit, &end_match);
+    uint32_t op = 0, anchor = sb, ip = sb;
+    bool have_first = false, overflow = false;
+    uint32_t first_mpos = kLbNone, first_mcode = 0;
+    while (ip < match_limit) {
+      const uint32_t pos = ip + lane;
+      uint32_t cand = 0xFFFFFFFFu, mlen = 0, h = 0;
+      if (pos < match_limit) {
+        const uint32_t v = lzb_read32<true>(src + (pos - base));
+        h = lz_hash(v);
+        const uint32_t c = table[h];
+        if (c != 0xFFFF && base + c < pos && lzb_read32<true>(src + c) == v) {
+          cand = base + c;
+          mlen = kLzMinMatch;
+          while (pos + mlen + 4 <= end_match &&
+                 lzb_read32<true>(src + (cand - base) + mlen) == lzb_read32<true>(src + (pos - base) + mlen))
+            mlen += 4;
+          while (pos + mlen < end_match && src[cand - base + mlen] == src[pos - base + mlen]) ++mlen;
+        }
+      }
+      __syncthreads();
+      if (pos < match_limit) table[h] = (uint16_t)(pos - base);  // last writer wins: any entry is verified
+      __syncthreads();
+      unsigned long long m = __ballot(cand != 0xFFFFFFFFu);
+      if (m == 0) { ip += kLzThreads; continue; }
+      unsigned long long sel = 0;
+      uint32_t my_lit = 0, last_end = ip, prev_end = anchor;
+      while (m) {
+        const int g = __ffsll((long long)m) - 1;
+        const uint32_t gml = __shfl(mlen, g);
+        if (lane == g) my_lit = prev_end;
+        sel |= 1ull << g;
+        prev_end = last_end = ip + g + gml;
+        const uint32_t skip = last_end - ip;
+        m = skip >= 64 ? 0ull : (m & (~0ull << skip));
+      }
+      const int g0 = __ffsll((long long)sel) - 1;
+      const bool is_first = !have_first && lane == g0;   // header + literals written by the merge
+      if (!have_first) {
+        first_mpos = ip + g0;
+        first_mcode = __shfl(mlen, g0) - 4;
+        have_first = true;
+      }
+      const bool mine = (sel >> lane) & 1ull;
+      const uint32_t lit = mine && !is_first ? pos - my_lit : 0;
+      const uint32_t need = !mine ? 0
+                          : is_first ? 2 + lz_len_bytes(mlen - 4)
+                                     : 1 + lz_len_bytes(lit) + lit + 2 + lz_len_bytes(mlen - 4);
+      uint32_t incl = need;
+#pragma unroll
+      for (int d = 1; d < kLzThreads; d <<= 1) {
+        const uint32_t tt = __shfl_up(incl, d);
+        if (lane >= d) incl += tt;
+      }
+      const uint32_t total = __shfl(incl, kLzThreads - 1);
+      if (op + total > seg_cap) { overflow = true; break; }
+      const uint32_t o = op + incl - need;
+      if (mine) {
+        const uint32_t mcode = mlen - 4;
+        const uint32_t moff = pos - cand;
+        uint32_t q = o;
+        if (!is_first) {
+          dst[q] = (uint8_t)(((lit >= 15 ? 15 : lit) << 4) | (mcode >= 15 ? 15 : mcode));
+          q = lz_put_len(dst, q + 1, lit) + lit;
+        }
+        dst[q] = (uint8_t)(moff & 255);
+        dst[q + 1] = (uint8_t)(moff >> 8);
+        lz_put_len(dst, q + 2, mcode);
+      }
+      unsigned long long rest = sel;
+      while (rest) {
+        const int g = __ffsll((long long)rest) - 1;
+        rest &= rest - 1;
+        const uint32_t gl = __shfl(lit, g);
+        if (gl == 0) continue;
+        const uint32_t gs = __shfl(my_lit, g);
+        const uint32_t go = __shfl(o, g) + 1 + lz_len_bytes(gl);
+        for (uint32_t i = lane; i < gl; i += kLzThreads) dst[go + i] = src[gs - base + i];
+      }
+      op += total;
+      anchor = prev_end;
+      ip = last_end > ip + kLzThreads ? last_end : ip + kLzThreads;
+    }
+    if (lane == 0) {
+      rec[kLbRecFirst] = first_mpos;
+      rec[kLbRecCode] = first_mcode;
+      rec[kLbRecBytes] = overflow ? kLbNone : op;
+      rec[kLbRecTail] = anchor;
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(kLzThreads) void lz4_page_link_kernel(const LbArgs a) {
+  const uint64_t p = (uint64_t)blockIdx.x * kLzThreads + threadIdx.x;
+  if (p < a.npages) lb_link_page(a, p);
+}
+
+__global__ __launch_bounds__(kLzMergeThreads) void lz4_page_merge_kernel(const LbArgs a) {
+  const uint32_t tid = threadIdx.x;
+  for (uint64_t t = blockIdx.x; t < a.nsegs; t += gridDim.x) {
+    LbMerge m;
+    lb_merge_plan(a, t, &m);                            // the same plan in every thread
+    if (m.head) {
+      if (tid == 0) lb_put_head(m);
+      uint8_t* q = m.dst + m.o + 1 + lb_len_bytes(m.lit);
+      for (uint32_t i = tid; i < m.lit; i += kLzMergeThreads) q[i] = m.src[m.P + i];
+      for (uint32_t i = tid; i < m.bytes; i += kLzMergeThreads) q[m.lit + i] = m.seq[i];
+    }
+    if (m.fin) {
+      if (tid == 0) lb_put_fin(m);
+      uint8_t* q = m.dst + m.fin_o + 1 + lb_len_bytes(m.fin_lit);
+      for (uint32_t i = tid; i < m.fin_lit; i += kLzMergeThreads) q[i] = m.src[m.fin_p + i];
+    }
+  }
+}
+
+static bool lz4_page_args_ok(const LbArgs& a, bool merge) {
+  constexpr uint64_t kMax = 1ull << 31;
+  if (a.npages == 0 || a.nsegs == 0 || a.npages > kMax || a.nsegs > kMax) return false;
+  if (!a.src || !a.pages || !a.segs || !a.scratch || !a.result) return false;
+  if (a.scratch_bytes < lb_scratch_head(a.nsegs) || (reinterpret_cast<uintptr_t>(a.scratch) & 3)) return false;
+  if (a.segment < 1 || (uint64_t)a.segment + a.warm > 65535) return false;
+  return !merge || (a.dst && a.out);
+}
+
+hipError_t launch_lz4_page_parse(const LbArgs& a, hipStream_t stream) {
+  if (!lz4_page_args_ok(a, false)) return hipErrorInvalidValue;
+  const size_t lds = (sizeof(uint16_t) << kLzHashLog) + (((size_t)a.segment + a.warm + 15) & ~(size_t)15);
+  hipLaunchKernelGGL(lz4_page_parse_kernel, dim3((unsigned)std::min<uint64_t>(a.nsegs, 65536)), dim3(kLzThreads), lds,
+                     stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_lz4_page_link(const LbArgs& a, hipStream_t stream) {
+  if (!lz4_page_args_ok(a, false)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(lz4_page_link_kernel, dim3((unsigned)((a.npages + kLzThreads - 1) / kLzThreads)),
+                     dim3(kLzThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_lz4_page_merge(const LbArgs& a, hipStream_t stream) {
+  if (!lz4_page_args_ok(a, true)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(lz4_page_merge_kernel, dim3((unsigned)std::min<uint64_t>(a.nsegs, 65536)),
+                     dim3(kLzMergeThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------
 // Synthetic data generator (bench / tests): splitmix64 of (seed, 8-byte word index).
 // ---------------------------------------------------------------------------------------------

@@ -8,6 +8,7 @@
 #pragma once
 #include <cstdint>
 
+#include "lz4_block_host.h"
 #include "parquet_encode_host.h"
 
 namespace amdx {
@@ -29,6 +30,19 @@ void parquet_encode_emit_raw(int pass, uint64_t pages, uint64_t npages, uint64_t
 // copy: nsegs rows of (source in blob, place in out, length).
 void parquet_encode_copy_raw(uint64_t blob, uint64_t blob_bytes, uint64_t segs, uint64_t nsegs, uint64_t out,
                              uint64_t out_bytes, int device, uint64_t stream);
+
+// LZ4_RAW: one LZ4 block per page body (lz4_block_host.h has the tables).  src holds the bodies;
+// pages (npages rows of kLbPageCols) and segs (nsegs rows of kLbSegCols) are the caller's tables;
+// scratch starts with lb_scratch_head(nsegs) bytes of records, 4-byte aligned, and the segment rows
+// name places behind them; result has npages rows of kLbResCols; no segment has more than `segment`
+// bytes and segment + warm <= 65535.  mode 0: parse and link (two
+// launches), after which result holds the blocks' sizes; mode 1: merge (one launch), every block
+// written at out + dst[page] (dst: npages int64).  With host memory every row is checked before
+// anything is written and what does not fit throws; on a device the kernels skip such rows and
+// flag their pages in result (kLbStatus).
+void parquet_encode_lz4_raw(int mode, uint64_t src, uint64_t src_bytes, uint64_t pages, uint64_t npages, uint64_t segs,
+                            uint64_t nsegs, uint64_t scratch, uint64_t scratch_bytes, uint64_t result, uint64_t dst,
+                            uint64_t out, uint64_t out_bytes, uint32_t warm, uint32_t segment, int device, uint64_t stream);
 
 // Kernel launches so far in this process (tests: a host call launches none, and the launches of a row
 // group do not depend on how many columns it has).

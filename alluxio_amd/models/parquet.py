@@ -33,8 +33,10 @@ The write side, :func:`write_parquet_columns` and :class:`ParquetWriter`, turns 
 :class:`FieldColumns` back into a file (``csrc/parquet_encode_host.h`` has the rules): measure (a
 flag per row and the sizes per page, the one readback), rank (``torch.cumsum``), emit (level bits,
 PLAIN values, text, bit-packed booleans and dictionary indices, and the host-built headers, all into
-one buffer per row group), then a footer from a small Thrift compact writer.  Uncompressed, V1 data
-pages, flat columns.  ``statistics=True`` has the device compute ``null_count``, ``min_value`` and
+one buffer per row group), then a footer from a small Thrift compact writer.  V1 data pages, flat
+columns; uncompressed, or with ``compression="lz4_raw"`` every page body as one LZ4 block made on
+the device (``csrc/lz4_block_host.h``: segments parsed by independent waves, linked and merged into
+one standard block per page, whatever its size).  ``statistics=True`` has the device compute ``null_count``, ``min_value`` and
 ``max_value`` of every column chunk (``csrc/parquet_stats_host.h`` has the rules;
 :func:`column_statistics` gives them for any :class:`FieldColumns`), and the readers take
 ``filters=`` to skip the row groups that the statistics of any file rule out.
@@ -1016,12 +1018,12 @@ class _ThriftOut:
         self._last.pop()
 
 
-def _page_header(page_type: int, size: int, num_values: int, encoding: int) -> bytes:
+def _page_header(page_type: int, size: int, num_values: int, encoding: int, compressed=None) -> bytes:
     t = _ThriftOut()
     t.struct()
     t.i32(1, page_type)
     t.i32(2, size)
-    t.i32(3, size)
+    t.i32(3, size if compressed is None else compressed)
     t.struct(5 if page_type == 0 else 7)
     t.i32(1, num_values)
     t.i32(2, encoding)
@@ -1195,7 +1197,7 @@ def column_statistics(columns) -> list:
 class _Group:
     """One row group on its way: the page table, the flat arrays and the measure table."""
     __slots__ = ("cols", "r0", "rows", "dev", "table", "index", "flags", "text_bytes", "measure", "flat_n", "layout",
-                 "stats")
+                 "stats", "bodies")
 
 
 def _measure_group(cols, r0, r1, page_rows, dev, statistics=False) -> _Group:
@@ -1254,14 +1256,23 @@ def _measure_group(cols, r0, r1, page_rows, dev, statistics=False) -> _Group:
     return g
 
 
-def _layout_group(g: _Group, invalid, dict_offsets) -> None:
+def _layout_group(g: _Group, invalid, dict_offsets, compressed=False) -> None:
     """The places of everything in the row group's buffer, from the measure table; everything that
     is refused from it is refused here.  ``g.layout``: the table with the dictionary pages added,
-    the copy segments, the blob, the buffer's size and, per column, what the footer needs."""
+    the copy segments, the blob, the buffer's size and, per column, what the footer needs.
+    ``g.bodies``: per page in file order ``(column, page type, values, encoding, where its header
+    starts, where its body starts, the body's bytes)``, which compression works from."""
     m, cols = g.measure, g.cols
     table = g.table.copy()
     extra, segs, blob, chunks = [], [], bytearray(), []
     pos = 0
+    g.bodies = []
+
+    def body_of(j, page_type, values, enc, header, size):
+        if compressed and _lz4_bound(size) >= _MAX_BODY:
+            raise ValueError(f"column {cols[j].name!r}: a page of {size} bytes, whose LZ4 block may take 2^31 bytes or "
+                             f"more; a page holds less than 2^31 (page_rows=)")
+        g.bodies.append((j, page_type, values, enc, pos, pos + len(header), size))
 
     def put(b: bytes):
         nonlocal pos
@@ -1290,7 +1301,9 @@ def _layout_group(g: _Group, invalid, dict_offsets) -> None:
             if body >= _MAX_BODY:
                 raise ValueError(f"column {c.name!r}: a dictionary page of {body} bytes; a page holds less than 2^31")
             dict_off = pos
-            put(_page_header(2, body, entries, 0))
+            header = _page_header(2, body, entries, 0)
+            body_of(j, 2, entries, 0, header, body)
+            put(header)
             row = np.zeros(_PE_COLS, dtype=np.int64)
             row[_E_KIND], row[_E_VALUES], row[_E_OFFSETS] = _K_TEXT, c.dictionary._data.data_ptr(), c.dictionary._off.data_ptr()
             row[_E_AUX], row[_E_ROWS], row[_E_LEVEL] = c.dictionary._nbytes, entries, -1
@@ -1322,7 +1335,9 @@ def _layout_group(g: _Group, invalid, dict_offsets) -> None:
             body = len(lev) + lev_bits + len(pre) + vb
             if body >= _MAX_BODY:
                 raise ValueError(f"column {c.name!r}: a page of {body} bytes; a page holds less than 2^31 (page_rows=)")
-            put(_page_header(0, body, rows, enc) + lev)
+            header = _page_header(0, body, rows, enc)
+            body_of(j, 0, rows, enc, header, body)
+            put(header + lev)
             table[p, _E_LEVEL] = pos if lev_bits else -1
             pos += lev_bits
             put(pre)
@@ -1377,6 +1392,108 @@ def _emit_group(g: _Group):
     return out
 
 
+# page, segment and result columns of csrc/lz4_block_host.h
+_LB_PAGE_COLS, _LB_SEG_COLS, _LB_RES_COLS = 4, 8, 4
+_LB_SIZE, _LB_STATUS = 0, 3
+_LB_SEGMENT, _LB_WARM = 32 * 1024, 4096
+_COMPRESSIONS = {None: 0, "none": 0, "uncompressed": 0, "lz4_raw": 7, "lz4": 7}
+
+
+def _lz4_bound(n: int) -> int:
+    return n + n // 255 + 16
+
+
+def _codec(compression) -> int:
+    key = compression.lower() if isinstance(compression, str) else compression
+    if key not in _COMPRESSIONS:
+        raise ValueError(f"compression is None, 'none', 'uncompressed', 'lz4_raw' or 'lz4' (both LZ4_RAW), "
+                         f"got {compression!r}")
+    return _COMPRESSIONS[key]
+
+
+def lz4_block_tables(bodies, segment=_LB_SEGMENT):
+    """The page and segment tables of ``csrc/lz4_block_host.h`` for page bodies ``(offset, length)``
+    of one source buffer, cut at ``segment`` bytes: ``(pages, segs, scratch_bytes)``, the tables as
+    int64 numpy arrays.  The segments' scratch areas lie behind the records, each of its LZ4 bound."""
+    bodies = [(int(o), int(n)) for o, n in bodies]
+    counts = [max(1, -(-n // segment)) for _o, n in bodies]
+    nsegs = sum(counts)
+    pages = np.zeros((len(bodies), _LB_PAGE_COLS), dtype=np.int64)
+    segs = np.zeros((nsegs, _LB_SEG_COLS), dtype=np.int64)
+    at, s = (nsegs * 24 + 15) & ~15, 0
+    for p, ((off, n), k) in enumerate(zip(bodies, counts)):
+        pages[p] = (off, n, s, k)
+        for i in range(k):
+            b, e = min(n, i * segment), min(n, (i + 1) * segment)
+            segs[s, :6] = (p, off, b, e, int(i + 1 == k), at)
+            at += (_lz4_bound(e - b) + 15) & ~15
+            s += 1
+    return pages, segs, at
+
+
+def _compress_group(g: _Group, staged, segment=_LB_SEGMENT, warm=_LB_WARM):
+    """The row group's staged bytes with every page body as one LZ4 block: parse and link over all
+    bodies, the second readback (the blocks' sizes), the page headers rebuilt on the host, and the
+    merge straight into the final buffer.  Returns ``(buffer, chunks)`` with the chunks' places and
+    compressed sizes in that buffer."""
+    import torch
+    from ..ops.native import lib, native_errors
+    C = lib()
+    dev = g.dev
+    device, stream = _queue(dev)
+    bodies = g.bodies
+    n = len(bodies)
+    pages, segs, scratch_bytes = lz4_block_tables([(b[5], b[6]) for b in bodies], segment)
+    both = _dev_i64(np.concatenate([pages.ravel(), segs.ravel()]), dev)
+    d_pages, d_segs = both[:pages.size], both[pages.size:]
+    scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
+    result = torch.zeros(n, _LB_RES_COLS, dtype=torch.int64, device=dev)
+
+    def run(mode, dst, out):
+        C.parquet_encode_lz4_raw(mode, _ptr(staged), staged.numel(), d_pages.data_ptr(), n, d_segs.data_ptr(), len(segs),
+                                 scratch.data_ptr(), scratch_bytes, result.data_ptr(), _ptr(dst), _ptr(out),
+                                 0 if out is None else out.numel(), min(warm, 65535 - segment), segment, device, stream)
+
+    with native_errors():
+        run(0, None, None)
+    host = result.cpu().numpy()                         # the second and last readback
+    if host[:, _LB_STATUS].any() or (host[:, _LB_SIZE] < 1).any():
+        p = int(np.nonzero((host[:, _LB_STATUS] != 0) | (host[:, _LB_SIZE] < 1))[0][0])
+        raise RuntimeError(f"column {g.cols[bodies[p][0]].name!r}: the LZ4 block of a page of {bodies[p][6]} bytes was "
+                           f"refused (status {int(host[p, _LB_STATUS])})")
+    sizes = host[:, _LB_SIZE]
+    blob, copies, dst = bytearray(), [], np.zeros(n, dtype=np.int64)
+    chunks, pos = [], 0
+    of_col = {}
+    for p, b in enumerate(bodies):
+        of_col.setdefault(b[0], []).append(p)
+    for j, (_d, _o, _total, enc) in enumerate(g.layout[4]):
+        start, dict_off, data_off = pos, None, None
+        for p in of_col[j]:
+            _col, page_type, values, penc, _h, _b, size = bodies[p]
+            if page_type == 2:
+                dict_off = pos
+            elif data_off is None:
+                data_off = pos
+            header = _page_header(page_type, size, values, penc, int(sizes[p]))
+            copies.append((len(blob), pos, len(header)))
+            blob.extend(header)
+            dst[p] = pos + len(header)
+            pos += len(header) + int(sizes[p])
+        if pos - start >= _MAX_BODY:
+            raise ValueError(f"column {g.cols[j].name!r}: a chunk of {pos - start} bytes; a chunk holds less than 2^31 "
+                             f"(row_group_rows=)")
+        chunks.append((dict_off, data_off, pos - start, enc))
+    out = torch.zeros(pos, dtype=torch.uint8, device=dev)
+    tabs = _dev_i64(np.concatenate([np.array(copies, dtype=np.int64).ravel(), dst]), dev)
+    d_blob = torch.from_numpy(np.frombuffer(bytes(blob), dtype=np.uint8).copy()).to(dev)
+    with native_errors():
+        C.parquet_encode_copy_raw(d_blob.data_ptr(), d_blob.numel(), tabs.data_ptr(), len(copies), out.data_ptr(), pos,
+                                  device, stream)
+        run(1, tabs[3 * len(copies):], out)
+    return out, chunks
+
+
 class ParquetWriter:
     """Writes :class:`FieldColumns` into one Parquet file, a row group per :meth:`write` call (or
     several, with ``row_group_rows``), encoded where the columns lie: device tensors by the kernels
@@ -1385,9 +1502,11 @@ class ParquetWriter:
     which :attr:`metadata` holds what :func:`parquet_metadata` would read.  See
     :func:`write_parquet_columns` for the format."""
 
-    def __init__(self, fs, path: str, required=(), page_rows=None, invalid="error", write_type=None, statistics=False):
+    def __init__(self, fs, path: str, required=(), page_rows=None, invalid="error", write_type=None, statistics=False,
+                 compression=None):
         if invalid not in ("error", "null"):
             raise ValueError("invalid is 'error' or 'null'")
+        self._codec = _codec(compression)
         if page_rows is not None and int(page_rows) < 1:
             raise ValueError("page_rows is at least 1")
         self.fs, self.path = fs, path
@@ -1437,17 +1556,20 @@ class ParquetWriter:
         groups = []
         for r0 in range(0, rows, max(step, 1)):
             g = _measure_group(cols, r0, min(rows, r0 + step), self.page_rows, dev, self.statistics)
-            _layout_group(g, self.invalid, self._dict_offsets)
+            _layout_group(g, self.invalid, self._dict_offsets, bool(self._codec))
             groups.append(g)
         self._schema, self._cols = schema, [(c.name, c.physical, c.kind, c.required) for c in cols]
         self._open()
         for g in groups:
-            out = _emit_group(g)
+            out, chunks = _emit_group(g), g.layout[4]
+            raw = [c[2] for c in chunks]                # the chunks' uncompressed bytes, headers included
+            if self._codec:
+                out, chunks = _compress_group(g, out)
             if dev.type == "cuda":
                 torch.cuda.current_stream(dev).synchronize()
             base = self._f.tell()
             self._f.write(out)
-            self._groups.append((g.rows, base, int(out.numel()), g.layout[4], g.stats))
+            self._groups.append((g.rows, base, int(out.numel()), chunks, g.stats, raw))
             self._rows += g.rows
 
     def _footer(self) -> bytes:
@@ -1473,7 +1595,7 @@ class ParquetWriter:
             t.end()
         t.i64(3, self._rows)
         t.list_(4, 12, len(self._groups))
-        for rows, base, size, chunks, stats in self._groups:
+        for rows, base, size, chunks, stats, raw in self._groups:
             t.struct()
             t.list_(1, 12, len(chunks))
             for j, ((name, physical, kind, required), (dict_off, data_off, total, enc)) in enumerate(zip(self._cols, chunks)):
@@ -1487,9 +1609,9 @@ class ParquetWriter:
                     t.b += _varint(e << 1)
                 t.list_(3, 8, 1)
                 t.b += _varint(len(name.encode())) + name.encode()
-                t.i32(4, 0)
+                t.i32(4, self._codec)
                 t.i64(5, rows)
-                t.i64(6, total)
+                t.i64(6, raw[j])
                 t.i64(7, total)
                 t.i64(9, base + data_off)
                 if dict_off is not None:
@@ -1504,7 +1626,7 @@ class ParquetWriter:
                     t.end()
                 t.end()
                 t.end()
-            t.i64(2, size)
+            t.i64(2, sum(raw))
             t.i64(3, rows)
             t.i64(5, base)
             t.i64(6, size)
@@ -1538,12 +1660,12 @@ class ParquetWriter:
         def read_back(physical, st):                    # what parquet_metadata makes of the bytes in the footer
             return None if st is None else ParquetStatistics(st[0], _stat_value(physical, st[1]), _stat_value(physical, st[2]))
 
-        groups = [ParquetRowGroup(rows, [ParquetChunk(name, physical, "UNCOMPRESSED", rows,
+        groups = [ParquetRowGroup(rows, [ParquetChunk(name, physical, CODECS[self._codec], rows,
                                                       None if d is None else base + d, base + o, total,
                                                       read_back(physical, stats and stats[j]))
                                          for j, ((name, physical, _k, _r), (d, o, total, _e))
                                          in enumerate(zip(self._cols, chunks))])
-                  for rows, base, _size, chunks, stats in self._groups]
+                  for rows, base, _size, chunks, stats, _raw in self._groups]
         self.metadata = ParquetMetadata(self._rows, leaves, groups, CREATED_BY)
 
     def abort(self) -> None:
@@ -1555,7 +1677,7 @@ class ParquetWriter:
 
 
 def write_parquet_columns(fs, path: str, columns, row_group_rows=None, page_rows=None, required=(), invalid="error",
-                          write_type=None, statistics=False) -> ParquetMetadata:
+                          write_type=None, statistics=False, compression=None) -> ParquetMetadata:
     """Writes ``columns`` (a :class:`FieldColumns` on a GPU or on the CPU) as the Parquet file
     ``path`` and returns its metadata.  The pages are encoded where the columns lie and each row
     group's bytes go to the output stream as one tensor on that device.
@@ -1567,12 +1689,22 @@ def write_parquet_columns(fs, path: str, columns, row_group_rows=None, page_rows
     dictionary's entries up to the largest code that the row group uses, and RLE_DICTIONARY data
     pages of one bit-packed run.  Columns are OPTIONAL (status 1 is a null; definition levels are one
     RLE run for a page without nulls, else one bit-packed run) unless named in ``required``.  Data
-    pages are V1 and nothing is compressed.
+    pages are V1.
+
+    ``compression``: ``None``, ``"none"`` or ``"uncompressed"`` write the pages as they are;
+    ``"lz4_raw"`` or ``"lz4"`` (pyarrow's name for codec 7) write every page body, dictionary pages
+    included, as one LZ4 block (codec LZ4_RAW), compressed where the columns lie; any other value is
+    a ``ValueError`` before the file is created.  A body is cut into segments of 32 KiB that are
+    parsed independently and stitched into one standard block (``csrc/lz4_block_host.h``), so the
+    blocks are a little larger than a serial encoder's and, on a device, need not be the same
+    bytes from run to run; what they decode to is.  An empty body is the one-byte block ``00``.  In
+    the footer ``total_uncompressed_size`` is what the chunk takes without compression and
+    ``total_compressed_size`` what it takes in the file.
 
     Refused before the file is created: a ``span`` column (``TypeError``); a status above 1, a
     deferred float included, unless ``invalid="null"`` writes such rows as nulls; a null in a
     required column; a live code outside its dictionary; a page or chunk of 2^31 bytes or more (all
-    ``ValueError``).
+    ``ValueError``); with compression, a page whose LZ4 bound reaches 2^31.
 
     ``statistics=True`` adds a ``Statistics`` struct to every column chunk (``null_count``, and
     ``min_value`` / ``max_value`` where :func:`column_statistics` gives bounds: PLAIN-encoded, so a
@@ -1586,9 +1718,12 @@ def write_parquet_columns(fs, path: str, columns, row_group_rows=None, page_rows
     columns there are; a category column's dictionary offsets are read once more when it has grown.
     With statistics: one more launch for numbers alone, ten with a text column and eleven with a
     category column (``csrc/parquet_stats.hip``), queued behind the measure launch, and their results
-    come back in that one readback."""
+    come back in that one readback.  With compression the row group is emitted into a staging
+    tensor and four more launches follow, however many pages and columns: parse and link, a second
+    small readback (the blocks' sizes, for the page headers), the copy of the rebuilt headers and
+    the merge of every block into its final place."""
     w = ParquetWriter(fs, path, required=required, page_rows=page_rows, invalid=invalid, write_type=write_type,
-                      statistics=statistics)
+                      statistics=statistics, compression=compression)
     try:
         w.write(columns, row_group_rows)
         w.close()
