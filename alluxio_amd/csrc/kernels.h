@@ -350,6 +350,8 @@ struct Lz4Chunk {
   uint32_t src_bytes;
   uint32_t dst_capacity;
 };
+constexpr int kLzThreads = 64;                 // one wave per chunk, in the decoders and the encoders
+constexpr uint32_t kLzWindow = 64 * 1024;      // the most bytes of a chunk
 hipError_t launch_lz4_decompress(const Lz4Chunk* chunks, int n, int32_t* out_sizes,
                                  hipStream_t stream);
 // 0: LDS-window decoder, 1: direct-to-HBM, 2 (default): direct + LDS-staged parse, 3: + LDS ring

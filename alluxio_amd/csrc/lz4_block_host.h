@@ -1,6 +1,6 @@
 // One standard LZ4 block per page body, of any size below 2^31: the rules, as plain C++.  A Parquet
 // LZ4_RAW page is a single block, so a page is cut into segments that are parsed independently and
-// stitched together again, as the 64 KiB chunk encoder of kernels.hip does in small:
+// stitched together again, as the 64 KiB chunk encoder of lz4_encode.hip does in small:
 //
 //   parse  one segment at a time (on the device: staged in LDS with the bytes before it, so the
 //          dependent loads of probe and match extension do not go to memory).  The hash table holds
@@ -26,8 +26,9 @@
 //
 // Written once and compiled twice, as parquet_encode_host.h is: the host loops (CPU columns, the
 // stand-alone check program) and, through PQ_HD, the rules, link and merge plan of the kernels in
-// kernels.hip.  The host parser is scalar and need not find the matches that the wave parse finds:
-// blocks are compared by what they decode to and by their sizes, never byte for byte.
+// lz4_encode.hip, whose chunk encoders also use the hash, the length bytes and the format constants
+// below.  The host parser is scalar and need not find the matches that the wave parse finds: its
+// blocks are compared with the device's by what they decode to and by their sizes, never byte for byte.
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -96,8 +97,14 @@ PQ_HD inline uint32_t lb_hash(uint32_t v) { return (v * 2654435761u) >> (32 - kL
 PQ_HD inline uint32_t lb_read32(const uint8_t* p) {
   return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
-PQ_HD inline uint32_t lb_len_bytes(uint32_t v) { return v >= 15 ? (v - 15) / 255 + 1 : 0; }
-PQ_HD inline uint64_t lb_put_len(uint8_t* dst, uint64_t q, uint32_t v) {
+PQ_HD inline uint32_t lb_len_bytes(uint32_t v) { return v >= 15 ? (v - 15) / 255 + 1 : 0; }   // after a 4-bit field
+PQ_HD inline uint8_t lb_token(uint32_t lit, uint32_t code) {
+  return (uint8_t)(((lit >= 15 ? 15 : lit) << 4) | (code >= 15 ? 15 : code));
+}
+// Q: the caller's position type.  The wave parse counts in 32 bits: with 64-bit positions here its
+// kernels take up to four more registers each.
+template <typename Q>
+PQ_HD inline Q lb_put_len(uint8_t* dst, Q q, uint32_t v) {
   if (v >= 15) {
     uint32_t r = v - 15;
     while (r >= 255) {
@@ -245,7 +252,7 @@ PQ_HD inline void lb_merge_plan(const LbArgs& a, uint64_t s, LbMerge* m) {
 }
 
 PQ_HD inline void lb_put_head(const LbMerge& m) {
-  m.dst[m.o] = (uint8_t)(((m.lit >= 15 ? 15 : m.lit) << 4) | (m.code >= 15 ? 15 : m.code));
+  m.dst[m.o] = lb_token(m.lit, m.code);
   lb_put_len(m.dst, m.o + 1, m.lit);
 }
 PQ_HD inline void lb_put_fin(const LbMerge& m) {
@@ -300,7 +307,7 @@ inline void lb_parse_segment_host(const LbArgs& a, uint64_t s) {
       rec[kLbRecCode] = code;
       first = false;
     } else {
-      dst[op] = (uint8_t)(((lit >= 15 ? 15 : lit) << 4) | (code >= 15 ? 15 : code));
+      dst[op] = lb_token(lit, code);
       op = lb_put_len(dst, op + 1, lit);
       std::memcpy(dst + op, src + anchor, lit);
       op += lit;

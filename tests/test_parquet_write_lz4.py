@@ -1,7 +1,8 @@
 """write_parquet_columns / ParquetWriter with compression="lz4_raw": every page body as one LZ4
-block made where the columns lie (csrc/lz4_block_host.h; the page kernels of csrc/kernels.hip).
-Blocks are compared by what they decode to and by their sizes: the device parse has a benign race
-in its hash table and need not give the same bytes twice.  The CPU variants run the host form on a
+block made where the columns lie (csrc/lz4_block_host.h; the page kernels of csrc/lz4_encode.hip).
+Blocks are compared here by what they decode to and by their sizes: the device parse has a benign
+race in its hash table, and the host parse is another one.  (The bytes the device has given so far
+are held by test_lz4_encode_golden.py.)  The CPU variants run the host form on a
 DRAM-tier cluster, the ``gpu`` ones the kernels on the HBM tier."""
 import io
 import os
@@ -75,7 +76,8 @@ def _conditions(kind, n, size):
 
 def _run_direct(device, segment=S):
     """parquet_encode_lz4_raw on bodies at odd offsets of one buffer: parse and link, the sizes,
-    merge; every block decodes with the host decoder to its body."""
+    merge; every block decodes with the host decoder to its body.  Returns the blocks by
+    (content, size)."""
     import torch
     from alluxio_amd.ops.native import lib
     C = lib()
@@ -122,7 +124,7 @@ def _run_direct(device, segment=S):
         _conditions(key[0], key[1], int(size))
         if key[1] == 0:
             assert block == b"\x00"
-        got[key] = int(size)
+        got[key] = block
     # a table row outside its buffer is refused (host: before anything runs)
     if dev.type == "cpu":
         from alluxio_amd.ops.native import native_errors
