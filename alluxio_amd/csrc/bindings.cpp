@@ -97,9 +97,11 @@ std::vector<uint32_t> crc32c_device_pages(uint64_t base, const std::vector<int64
   return out;
 }
 
-// chunks: list of (src_ptr, dst_ptr, src_bytes, dst_capacity) on the device
-std::vector<int32_t> lz4_device(const std::vector<std::tuple<uint64_t, uint64_t, uint32_t, uint32_t>>& chunks,
-                                bool compress, uint64_t stream) {
+// chunks: list of (src_ptr, dst_ptr, src_bytes, dst_capacity) on the device; `launch`: the codec
+using ChunkList = std::vector<std::tuple<uint64_t, uint64_t, uint32_t, uint32_t>>;
+using ChunkLaunch = hipError_t (*)(const Lz4Chunk*, int, int32_t*, hipStream_t);
+
+std::vector<int32_t> chunks_device(const ChunkList& chunks, ChunkLaunch launch, uint64_t stream) {
   const int n = (int)chunks.size();
   std::vector<int32_t> sizes(n, 0);
   if (!n) return sizes;
@@ -113,17 +115,15 @@ std::vector<int32_t> lz4_device(const std::vector<std::tuple<uint64_t, uint64_t,
   ScratchBuf dch(sizeof(Lz4Chunk) * n), dsz(sizeof(int32_t) * n);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   HIP_CHECK(hipMemcpyAsync(dch.p, h.data(), sizeof(Lz4Chunk) * n, hipMemcpyHostToDevice, st));
-  if (compress) HIP_CHECK(launch_lz4_compress((Lz4Chunk*)dch.p, n, (int32_t*)dsz.p, st));
-  else HIP_CHECK(launch_lz4_decompress((Lz4Chunk*)dch.p, n, (int32_t*)dsz.p, st));
+  HIP_CHECK(launch((Lz4Chunk*)dch.p, n, (int32_t*)dsz.p, st));
   HIP_CHECK(hipMemcpyAsync(sizes.data(), dsz.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
   return sizes;
 }
 
-// Kernel-only timing of an LZ4 batch: the chunk table is uploaded once, `reps` launches are
+// Kernel-only timing of a batch: the chunk table is uploaded once, `reps` launches are
 // bracketed by HIP events (no per-call allocation / table upload / size download in the number).
-double lz4_device_kernel_ms(const std::vector<std::tuple<uint64_t, uint64_t, uint32_t, uint32_t>>& chunks,
-                            bool compress, int reps) {
+double chunks_device_kernel_ms(const ChunkList& chunks, ChunkLaunch launch_codec, int reps) {
   const int n = (int)chunks.size();
   if (!n || reps <= 0) return 0.0;
   std::vector<Lz4Chunk> h(n);
@@ -134,10 +134,7 @@ double lz4_device_kernel_ms(const std::vector<std::tuple<uint64_t, uint64_t, uin
   hipEvent_t a, b;
   HIP_CHECK(hipEventCreate(&a));
   HIP_CHECK(hipEventCreate(&b));
-  auto launch = [&] {
-    if (compress) HIP_CHECK(launch_lz4_compress((Lz4Chunk*)dch.p, n, (int32_t*)dsz.p, 0));
-    else HIP_CHECK(launch_lz4_decompress((Lz4Chunk*)dch.p, n, (int32_t*)dsz.p, 0));
-  };
+  auto launch = [&] { HIP_CHECK(launch_codec((Lz4Chunk*)dch.p, n, (int32_t*)dsz.p, 0)); };
   launch();
   HIP_CHECK(hipEventRecord(a, 0));
   for (int r = 0; r < reps; ++r) launch();
@@ -148,6 +145,19 @@ double lz4_device_kernel_ms(const std::vector<std::tuple<uint64_t, uint64_t, uin
   (void)hipEventDestroy(a);
   (void)hipEventDestroy(b);
   return ms / reps;
+}
+
+std::vector<int32_t> lz4_device(const ChunkList& chunks, bool compress, uint64_t stream) {
+  return chunks_device(chunks, compress ? launch_lz4_compress : launch_lz4_decompress, stream);
+}
+double lz4_device_kernel_ms(const ChunkList& chunks, bool compress, int reps) {
+  return chunks_device_kernel_ms(chunks, compress ? launch_lz4_compress : launch_lz4_decompress, reps);
+}
+std::vector<int32_t> snappy_device(const ChunkList& chunks, uint64_t stream) {
+  return chunks_device(chunks, launch_snappy_decompress, stream);
+}
+double snappy_device_kernel_ms(const ChunkList& chunks, int reps) {
+  return chunks_device_kernel_ms(chunks, launch_snappy_decompress, reps);
 }
 
 // Process-wide descriptor ring for ad-hoc batched copies (IPC reads, peer pulls): no per-call
@@ -808,6 +818,16 @@ PYBIND11_MODULE(_C, m) {
         py::arg("data"), py::arg("data_bytes"), py::arg("table"), py::arg("npages"), py::arg("dst_off"), py::arg("out"),
         py::arg("out_bytes"), py::arg("chunks"), py::arg("expect"), py::arg("sizes"), py::arg("device"),
         py::arg("stream") = 0);
+  m.def("parquet_decompress_raw",
+        [](int codec, uint64_t data, uint64_t data_bytes, uint64_t table, uint64_t npages, uint64_t dst_off, uint64_t out,
+           uint64_t out_bytes, uint64_t chunks, uint64_t expect, uint64_t sizes, int device, uint64_t stream) {
+          py::gil_scoped_release rel;
+          parquet_decompress_raw(codec, data, data_bytes, table, npages, dst_off, out, out_bytes, chunks, expect, sizes,
+                                 device, stream);
+        },
+        py::arg("codec"), py::arg("data"), py::arg("data_bytes"), py::arg("table"), py::arg("npages"),
+        py::arg("dst_off"), py::arg("out"), py::arg("out_bytes"), py::arg("chunks"), py::arg("expect"), py::arg("sizes"),
+        py::arg("device"), py::arg("stream") = 0);
   m.def("parquet_hybrid_raw",
         [](uint64_t data, uint64_t data_bytes, uint64_t streams, uint64_t nstreams, uint64_t out, uint64_t out_n,
            uint64_t errors, int device, int mode, uint64_t run_counts, uint64_t run_base, uint64_t runs,
@@ -1285,12 +1305,48 @@ PYBIND11_MODULE(_C, m) {
           return py::bytes(out);
         });
   m.def("lz4_compress_bound", &lz4_compress_bound);
+  // one Snappy raw stream on the host (csrc/snappy_host.h); `capacity` is the size its preamble has to give
+  m.def("snappy_decompress", [](py::bytes data, size_t capacity) {
+          std::string s = data;
+          std::string out(capacity, '\0');
+          int64_t n;
+          {
+            py::gil_scoped_release rel;
+            n = snappy_decompress_block((const uint8_t*)s.data(), s.size(), (uint8_t*)&out[0], out.size());
+          }
+          if (n < 0) throw StoreError(kErrInvalidArgument, "malformed snappy stream (" + std::to_string(n) + ")");
+          out.resize((size_t)n);
+          return py::bytes(out);
+        }, py::arg("data"), py::arg("capacity"));
+  // the same over streams laid out in host memory at addresses, as snappy_device takes them on the device
+  m.def("snappy_host", [](const ChunkList& chunks) {
+          py::gil_scoped_release rel;
+          std::vector<int32_t> sizes(chunks.size());
+          for (size_t i = 0; i < chunks.size(); ++i)
+            sizes[i] = (int32_t)snappy_decompress_block(reinterpret_cast<const uint8_t*>(std::get<0>(chunks[i])),
+                                                        std::get<2>(chunks[i]),
+                                                        reinterpret_cast<uint8_t*>(std::get<1>(chunks[i])),
+                                                        std::get<3>(chunks[i]));
+          return sizes;
+        }, py::arg("chunks"));
+  m.def("snappy_decode_sizes", [] {
+    py::dict d;
+    d["stage0"] = kSnStage0;
+    d["stage"] = kSnStage;
+    d["ring"] = kSnRing;
+    d["window"] = kSnWindow;
+    d["flush"] = kSnFlush;
+    d["default_variant"] = kSnDefaultVariant;
+    return d;
+  });
   m.def("trace_push", [](const std::string& name) { roctxRangePushA(name.c_str()); }, py::arg("name"));
   m.def("trace_pop", [] { roctxRangePop(); });
   m.def("trace_mark", [](const std::string& name) { roctxMarkA(name.c_str()); }, py::arg("name"));
   m.def("lz4_device", &lz4_device, G(), py::arg("chunks"), py::arg("compress"), py::arg("stream") = 0);
   m.def("lz4_device_kernel_ms", &lz4_device_kernel_ms, G(), py::arg("chunks"), py::arg("compress"),
         py::arg("reps") = 5);
+  m.def("snappy_device", &snappy_device, G(), py::arg("chunks"), py::arg("stream") = 0);
+  m.def("snappy_device_kernel_ms", &snappy_device_kernel_ms, G(), py::arg("chunks"), py::arg("reps") = 5);
   m.def("batched_copy", &batched_copy, G(), py::arg("segments"), py::arg("stream") = 0, py::arg("sync") = true);
   m.def("fill_pattern", [](uint64_t ptr, uint64_t bytes, uint64_t seed, uint64_t word_offset, uint64_t stream) {
           py::gil_scoped_release rel;
@@ -1319,6 +1375,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("set_crc_variant", &set_crc_variant, py::arg("variant"));
   m.def("set_lz4_decode_variant", &set_lz4_decode_variant, py::arg("variant"));
   m.def("set_lz4_encode_variant", &set_lz4_encode_variant, py::arg("variant"));
+  m.def("set_snappy_decode_variant", &set_snappy_decode_variant, py::arg("variant"));
   m.def("set_seq_read_variant", &set_seq_read_variant, py::arg("variant"), py::arg("grid_cap") = 0);
   m.def("seq_read_variant", [] {
     int v = 0;

@@ -5,6 +5,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "snappy_host.h"
+
 namespace amdx {
 
 uint32_t crc32c_sw(const void* data, size_t n, uint32_t crc = 0);  // standard (init/xorout ~0)
@@ -21,5 +23,7 @@ int64_t lz4_compress_block(const uint8_t* src, size_t n, uint8_t* dst, size_t ds
 // Returns decompressed size, or a negative error code on malformed input / overflow.
 int64_t lz4_decompress_block(const uint8_t* src, size_t n, uint8_t* dst, size_t dst_cap);
 size_t lz4_compress_bound(size_t n);
+// Snappy raw streams: snappy_decompress_block(src, n, dst, cap) of snappy_host.h, inline there because
+// the kernels compile the same rules.  Returns cap, or a negative code on a malformed stream.
 
 }  // namespace amdx

@@ -362,6 +362,18 @@ void set_lz4_encode_variant(int v);
 // the chunk does not fit dst_capacity (caller then stores it raw).
 hipError_t launch_lz4_compress(const Lz4Chunk* chunks, int n, int32_t* out_sizes,
                                hipStream_t stream);
+// Snappy raw decompression of `n` independent streams (snappy_decode.hip; snappy_host.h has the
+// format and the codes): the chunk table of launch_lz4_decompress, out_sizes[i] the bytes produced
+// (dst_capacity, which the stream's preamble has to equal) or a negative code.  One wave per stream.
+// 0: one element per step; 1: a 64-byte window of the stream per step; -1: the default.
+constexpr int kSnDefaultVariant = 1;
+constexpr uint32_t kSnStage0 = 2048;           // variant 0: bytes of the stream staged in LDS
+constexpr uint32_t kSnStage = 1024;            // variant 1: the stage,
+constexpr uint32_t kSnRing = 4096;             //   the LDS ring of recent output,
+constexpr uint32_t kSnWindow = 256;            //   the most output bytes of one step,
+constexpr uint32_t kSnFlush = 1024;            //   and the bytes after which the ring goes to HBM
+hipError_t launch_snappy_decompress(const Lz4Chunk* chunks, int n, int32_t* out_sizes, hipStream_t stream);
+void set_snappy_decode_variant(int v);
 // One LZ4 block per page body of any size below 2^31 (lz4_block_host.h has the tables and the
 // rules): parse (one wave per segment row, sequences and records into scratch), link (one lane per
 // page: the places of the segments and the sizes into `result`) and merge (one workgroup per

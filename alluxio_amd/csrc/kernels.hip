@@ -2,6 +2,7 @@
 // and are capped so a launch always drains.  See kernels.h for the reference hot loops each
 // kernel replaces.
 #include "kernels.h"
+#include "lz_wave.h"
 
 #include <algorithm>
 #include <cstring>
@@ -1758,14 +1759,7 @@ __global__ __launch_bounds__(kLzThreads) void lz4_decompress_ring_kernel(const L
 //     64 bytes instead of one per byte;
 //   * output goes to HBM with plain stores that are never read back, except by far matches
 //     (offset > R-64), which fence only when their source overlaps unfenced output.
-__device__ __forceinline__ void lz_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-typedef __attribute__((address_space(1))) uint8_t gu8;
-
+// (lz_wave_sync, the wave barrier between LDS writes and reads of other lanes, and gu8 are in lz_wave.h)
 template <uint32_t R, bool kFast, uint32_t I = kLzIn>
 __global__ __launch_bounds__(kLzThreads) void lz4_decompress_wave_kernel(const Lz4Chunk* __restrict__ ch,
                                                                         int n, int32_t* __restrict__ out_sizes) {
@@ -2115,23 +2109,7 @@ __global__ __launch_bounds__(kLzThreads) void lz4_decompress_groups_kernel(const
 //      aligned 16-byte vectors every 1 KiB.
 // Sequences whose header or output does not fit a window (long literal runs, long matches) go
 // through a per-sequence path that copies with all 64 lanes straight from HBM.
-__device__ __forceinline__ uint32_t lz_shfl(uint32_t v, uint32_t src) { return (uint32_t)__shfl((int)v, (int)src, 64); }
-__device__ __forceinline__ uint32_t lz_scan_add(uint32_t v, uint32_t lane) {
-#pragma unroll
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint32_t t = (uint32_t)__shfl_up((int)v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t lz_scan_max(uint32_t v, uint32_t lane) {
-#pragma unroll
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint32_t t = (uint32_t)__shfl_up((int)v, o, 64);
-    if (lane >= o) v = v > t ? v : t;
-  }
-  return v;
-}
+// (lz_shfl, lz_scan_add and lz_scan_max are in lz_wave.h)
 
 // kVec (variants 23-25): the walk and the code build without per-sequence scalar work.  PMC of the
 // scalar walk (profiles/r3_lz4_window.md) showed ~36 SALU instructions per sequence, and the CU's

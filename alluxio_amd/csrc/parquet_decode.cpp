@@ -14,6 +14,7 @@ namespace {
 
 std::atomic<uint64_t> g_pq_launches{0};
 constexpr uint64_t kMax = 1ull << 31;
+constexpr int kPqCodecSnappy = 1, kPqCodecLz4Raw = 7;   // CompressionCodec of the format
 
 void bad(const std::string& what) { throw StoreError(kErrInvalidArgument, "parquet decode: " + what); }
 
@@ -55,6 +56,15 @@ void parquet_walk_raw(uint64_t data, uint64_t data_bytes, uint64_t chunk_off, ui
 void parquet_lz4_raw(uint64_t data, uint64_t data_bytes, uint64_t table, uint64_t npages, uint64_t dst_off,
                      uint64_t out, uint64_t out_bytes, uint64_t chunks, uint64_t expect, uint64_t sizes, int device,
                      uint64_t stream) {
+  parquet_decompress_raw(kPqCodecLz4Raw, data, data_bytes, table, npages, dst_off, out, out_bytes, chunks, expect, sizes,
+                         device, stream);
+}
+
+void parquet_decompress_raw(int codec, uint64_t data, uint64_t data_bytes, uint64_t table, uint64_t npages,
+                            uint64_t dst_off, uint64_t out, uint64_t out_bytes, uint64_t chunks, uint64_t expect,
+                            uint64_t sizes, int device, uint64_t stream) {
+  if (codec != kPqCodecSnappy && codec != kPqCodecLz4Raw) bad("no decoder for codec " + std::to_string(codec));
+  const bool snappy = codec == kPqCodecSnappy;
   if (npages > kMax) bad("too many pages for one call");
   PqLz4Args a{};
   a.data = ptr<const uint8_t>(data);
@@ -75,16 +85,19 @@ void parquet_lz4_raw(uint64_t data, uint64_t data_bytes, uint64_t table, uint64_
     int32_t* sz = ptr<int32_t>(sizes);
     for (uint64_t p = 0; p < npages; ++p) {
       const PqLz4Chunk& c = a.chunks[p];
-      sz[p] = c.src_bytes == 0 ? 0
-                               : (int32_t)lz4_decompress_block(ptr<const uint8_t>(c.src), c.src_bytes,
-                                                               ptr<uint8_t>(c.dst), c.dst_capacity);
+      if (c.src_bytes == 0) sz[p] = 0;
+      else if (snappy)
+        sz[p] = (int32_t)snappy_decompress_block(ptr<const uint8_t>(c.src), c.src_bytes, ptr<uint8_t>(c.dst), c.dst_capacity);
+      else
+        sz[p] = (int32_t)lz4_decompress_block(ptr<const uint8_t>(c.src), c.src_bytes, ptr<uint8_t>(c.dst), c.dst_capacity);
     }
     return;
   }
   AMDX_HIP(hipSetDevice(device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   AMDX_HIP(launch_parquet_lz4_plan(a, st));
-  AMDX_HIP(launch_lz4_decompress(reinterpret_cast<const Lz4Chunk*>(a.chunks), (int)npages, ptr<int32_t>(sizes), st));
+  AMDX_HIP((snappy ? launch_snappy_decompress : launch_lz4_decompress)(reinterpret_cast<const Lz4Chunk*>(a.chunks),
+                                                                      (int)npages, ptr<int32_t>(sizes), st));
   g_pq_launches += 2;
 }
 

@@ -24,6 +24,12 @@ void parquet_walk_raw(uint64_t data, uint64_t data_bytes, uint64_t chunk_off, ui
 void parquet_lz4_raw(uint64_t data, uint64_t data_bytes, uint64_t table, uint64_t npages, uint64_t dst_off,
                      uint64_t out, uint64_t out_bytes, uint64_t chunks, uint64_t expect, uint64_t sizes, int device,
                      uint64_t stream);
+// The same for the pages of any codec that has a decoder: `codec` is the format's number, 1 (SNAPPY:
+// the Snappy raw decoder) or 7 (LZ4_RAW); another one is an invalid argument.  parquet_lz4_raw is
+// codec 7.  Two launches per call on a device, none on the host.
+void parquet_decompress_raw(int codec, uint64_t data, uint64_t data_bytes, uint64_t table, uint64_t npages,
+                            uint64_t dst_off, uint64_t out, uint64_t out_bytes, uint64_t chunks, uint64_t expect,
+                            uint64_t sizes, int device, uint64_t stream);
 
 // Hybrid streams.  mode 0: each stream decoded serially (the host loop; kernel variant 0).  The
 // cooperative form is three calls: mode 1 counts the runs (run_counts, errors), mode 2 fills the run

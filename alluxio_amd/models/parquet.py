@@ -8,7 +8,8 @@ yields one :class:`FieldColumns` per row group for a training loop.
 
 The passes (``csrc/parquet_host.h`` has the rules in full): the page walk parses the
 ``PageHeader`` between the pages of every chunk into a page table; LZ4_RAW pages are decompressed
-by the LZ4 block kernel into a second buffer; definition levels, dictionary indices and RLE
+by the LZ4 block kernel and, where the call allows it (``codecs=``), SNAPPY pages by the Snappy
+kernel (``csrc/snappy_host.h`` has the format) into a second buffer; definition levels, dictionary indices and RLE
 booleans are RLE / bit-packed hybrid streams decoded to int32; a row then takes value number
 ``rank`` of its page (``rank``: the exclusive prefix sum of validity within the page) from PLAIN
 bytes or from the chunk's dictionary; a PLAIN BYTE_ARRAY page is walked into spans that
@@ -24,8 +25,9 @@ column comes back as its ``int64``, a decimal as its integer, a date as its ``in
 
 Not supported (``NotImplementedError`` that names the column, before any launch unless noted):
 columns with repetition or a definition level above 1 (lists, structs with optional parents),
-INT96 and FIXED_LEN_BYTE_ARRAY, every codec but UNCOMPRESSED and LZ4_RAW (so SNAPPY, GZIP, ZSTD,
-BROTLI and the Hadoop-framed LZ4), BIT_PACKED levels, encrypted files, and the DELTA_* and
+INT96 and FIXED_LEN_BYTE_ARRAY, every codec but UNCOMPRESSED, LZ4_RAW and, only when the call names
+it in ``codecs=`` (``codecs=("LZ4_RAW", "SNAPPY")`` or ``codecs="all"``), SNAPPY (so GZIP, ZSTD,
+BROTLI and the Hadoop-framed LZ4 always), BIT_PACKED levels, encrypted files, and the DELTA_* and
 BYTE_STREAM_SPLIT value encodings, which only a page header reveals and which are therefore
 raised after the page walk.  Columns that are not selected may be of any kind.
 
@@ -317,9 +319,34 @@ def _type_code(dtype) -> int:
                          f"category") from None
 
 
-def _plan(path, md: ParquetMetadata, columns, row_groups):
+# the codecs that have a decoder, by the names a caller may give (pyarrow calls codec 7 "LZ4")
+_DECODERS = {"LZ4_RAW": "LZ4_RAW", "LZ4": "LZ4_RAW", "SNAPPY": "SNAPPY"}
+_DEFAULT_CODECS = ("LZ4_RAW",)
+
+
+def _allowed_codecs(codecs) -> tuple:
+    """The ``codecs=`` argument as the names of :data:`CODECS` that a call may decode besides
+    UNCOMPRESSED, LZ4_RAW first (the order in which a refusal lists them)."""
+    if codecs is None:
+        names = _DEFAULT_CODECS
+    elif isinstance(codecs, str) and codecs.lower() == "all":
+        names = tuple(_DECODERS.values())
+    else:
+        names = []
+        for c in [codecs] if isinstance(codecs, str) else codecs:
+            key = c.upper() if isinstance(c, str) else c
+            if key == "UNCOMPRESSED":
+                continue
+            if key not in _DECODERS:
+                raise ValueError(f"codecs names codecs that have a decoder, {sorted(_DECODERS)} (or 'all'), got {c!r}")
+            names.append(_DECODERS[key])
+    return tuple(sorted(set(names), key=CODECS.index, reverse=True))
+
+
+def _plan(path, md: ParquetMetadata, columns, row_groups, codecs=None):
     """[(name or None, leaf position, leaf, type code)] and the row group numbers, with everything
-    that can be refused from the footer refused."""
+    that can be refused from the footer refused.  ``codecs``: what :func:`_allowed_codecs` gave."""
+    allowed = _allowed_codecs(None) if codecs is None else codecs
     by_name = {lf.name: j for j, lf in enumerate(md.schema)}
     if columns is None:
         items = [(lf.name, (lf.name, None)) for lf in md.schema
@@ -364,9 +391,13 @@ def _plan(path, md: ParquetMetadata, columns, row_groups):
             if j >= len(rg.columns):
                 raise ValueError(f"{path}: row group {g} has no chunk for column {lf.name!r}")
             cc = rg.columns[j]
-            if cc.codec not in ("UNCOMPRESSED", "LZ4_RAW"):
+            if cc.codec != "UNCOMPRESSED" and cc.codec not in allowed:
+                names = ("UNCOMPRESSED",) + allowed
+                only = f"{', '.join(names[:-1])} and {names[-1]} are" if allowed else "UNCOMPRESSED is"
+                hint = (f" (pass codecs=(..., {cc.codec!r}) or codecs='all' to have it decoded)"
+                        if cc.codec in _DECODERS.values() else "")
                 raise NotImplementedError(f"{path}: column {lf.name!r} is compressed with {cc.codec}; only "
-                                          f"UNCOMPRESSED and LZ4_RAW are supported")
+                                          f"{only} supported{hint}")
     return specs, groups
 
 
@@ -584,10 +615,12 @@ def _byte_spans(data, pages, excl, rows, stream_err, nvalues):
     return start, length, status
 
 
-def _decompress(data, table, sel):
-    """The pages ``sel`` (rows of the host page table) of LZ4_RAW chunks decompressed into a second
+def _decompress(data, table, sel, codecs):
+    """The pages ``sel`` (rows of the host page table) of compressed chunks decompressed into a second
     buffer: ``(buffer, rows)`` where ``rows`` are those pages' table rows rewritten to point into the
-    buffer as uncompressed pages; a page whose LZ4 block is malformed gets type -1."""
+    buffer as uncompressed pages; a page whose stream is malformed, or gives another size than its
+    header states, gets type -1.  ``codecs``: the codec number of every page of ``sel``; the pages of
+    all codecs share the buffer, and each codec present takes one native call."""
     import torch
     from ..ops.native import lib, native_errors
     dev = data.device
@@ -598,13 +631,22 @@ def _decompress(data, table, sel):
     out = torch.zeros(int(dst[-1]), dtype=torch.uint8, device=dev)
     if n == 0:
         return out, rows
-    d_table, d_dst = _dev_i64(rows, dev), _dev_i64(dst[:-1], dev)
+    codecs = np.asarray(codecs, dtype=np.int64)
+    order = np.argsort(codecs, kind="stable")           # the pages of one codec in a row
+    d_table, d_dst = _dev_i64(rows[order], dev), _dev_i64(dst[:-1][order], dev)
     chunks = torch.zeros(n * 3, dtype=torch.int64, device=dev)
     got = torch.zeros(2, n, dtype=torch.int32, device=dev)      # expected, produced
+    at = 0
     with native_errors():
-        lib().parquet_lz4_raw(_ptr(data), data.numel(), d_table.data_ptr(), n, d_dst.data_ptr(), _ptr(out), out.numel(),
-                              chunks.data_ptr(), got[0].data_ptr(), got[1].data_ptr(), device, stream)
-    bad = (got[0] != got[1]).cpu().numpy()
+        for codec in np.unique(codecs):
+            m = int((codecs == codec).sum())
+            lib().parquet_decompress_raw(int(codec), _ptr(data), data.numel(), d_table.data_ptr() + at * rows.shape[1] * 8,
+                                         m, d_dst.data_ptr() + at * 8, _ptr(out), out.numel(),
+                                         chunks.data_ptr() + at * 24, got[0].data_ptr() + at * 4,
+                                         got[1].data_ptr() + at * 4, device, stream)
+            at += m
+    bad = np.zeros(n, dtype=bool)
+    bad[order] = (got[0] != got[1]).cpu().numpy()
     rows[:, _T_PAYLOAD] = dst[:-1]
     rows[:, _T_COMP] = rows[:, _T_UNCOMP]
     rows[:, _T_ISCOMP] = 0
@@ -833,11 +875,12 @@ def _row_group(path, dl, records, sizes, rg, specs, dicts):
     base = np.concatenate([[0], np.cumsum(counts)])
     for k, (_n, j, lf, _t) in enumerate(specs):
         _check_pages(path, lf, table[base[k]:base[k + 1]])
-    packed = np.array([rg.columns[j].codec == "LZ4_RAW" for _n, j, _lf, _t in specs])
+    codec = np.array([CODECS.index(rg.columns[j].codec) for _n, j, _lf, _t in specs])
+    packed = codec != 0                                 # not UNCOMPRESSED
     sel = np.nonzero(packed[table[:, _T_CHUNK]])[0] if len(table) else np.zeros(0, np.int64)
     buf2 = None
     if len(sel):
-        buf2, rows2 = _decompress(data, table, sel)
+        buf2, rows2 = _decompress(data, table, sel, codec[table[sel, _T_CHUNK]])
         table = table.copy()
         table[sel] = rows2
     bufs = [buf2 if packed[k] and buf2 is not None else data for k in range(len(specs))]
@@ -868,17 +911,18 @@ def _row_group(path, dl, records, sizes, rg, specs, dicts):
 
 
 def parquet_row_groups(fs, path: str, columns=None, row_groups=None, device=None, device_plan="auto",
-                       dictionaries=None, filters=None):
+                       dictionaries=None, filters=None, codecs=None):
     """A generator of one :class:`FieldColumns` per row group (``row_groups``: their numbers, in the
     order wanted; ``None``: all; with ``filters``, those of them that the statistics cannot rule
     out), for a training loop that takes a file piece by piece.  Arguments are those of
     :func:`read_parquet_columns`; a category column's dictionary is shared by all row groups.  The
     footer is read and everything it can refuse is refused when the generator is created, not at the
     first ``next``."""
+    allowed = _allowed_codecs(codecs)
     md = parquet_metadata(fs, path)
     if filters is not None:
         row_groups = _matching(path, md, _filters(path, md, filters), row_groups)
-    specs, groups = _plan(path, md, columns, row_groups)
+    specs, groups = _plan(path, md, columns, row_groups, allowed)
     return _row_group_iter(fs, path, md, specs, groups, device, device_plan, dictionaries)
 
 
@@ -912,7 +956,7 @@ def _row_group_iter(fs, path, md, specs, groups, device, device_plan, dictionari
 
 
 def read_parquet_columns(fs, path: str, columns=None, row_groups=None, device=None, device_plan="auto",
-                         dictionaries=None, filters=None) -> FieldColumns:
+                         dictionaries=None, filters=None, codecs=None) -> FieldColumns:
     """The selected columns of a Parquet file as tensors on ``device``, decoded where the bytes lie.
 
     ``columns``: ``None`` (every supported leaf, with the type its physical type implies), a list of
@@ -938,6 +982,12 @@ def read_parquet_columns(fs, path: str, columns=None, row_groups=None, device=No
     nesting, physical type) is refused for the kept row groups only.  With every row group pruned the
     result has no rows, the requested columns and types, and nothing is gathered or launched.
 
+    ``codecs`` names the codecs the call may decode besides UNCOMPRESSED: ``None`` is
+    ``("LZ4_RAW",)``; ``("LZ4_RAW", "SNAPPY")`` or ``"all"`` (every codec that has a decoder) also
+    reads Snappy chunks, which Parquet writers make by default.  Names are case-insensitive and
+    ``"LZ4"`` is pyarrow's name for LZ4_RAW; a name without a decoder (``"GZIP"``, ``"ZSTD"``, ...)
+    is a ``ValueError``.  A row group may mix the codecs; every codec present costs two launches.
+
     The bytes of the selected column chunks, and only those, come through a
     :class:`DeviceBatchLoader` over the file cut at chunk boundaries: one ragged gather per row group
     when the file is cached in device memory by one in-process worker (``device_plan="auto"``); a
@@ -945,7 +995,7 @@ def read_parquet_columns(fs, path: str, columns=None, row_groups=None, device=No
     row group the page table, a flag per LZ4 page and the sizes that text columns, dictionaries and
     (in kernel variant 1) run tables need are read back; everything else stays on torch's current
     stream.  See the module's documentation for types, statuses and what is refused."""
-    parts = list(parquet_row_groups(fs, path, columns, row_groups, device, device_plan, dictionaries, filters))
+    parts = list(parquet_row_groups(fs, path, columns, row_groups, device, device_plan, dictionaries, filters, codecs))
     return FieldColumns.concat(parts)
 
 

@@ -20,9 +20,9 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM, "bin", "hipcc")
 
-SOURCES = ["kernels.hip", "lz4_encode.hip", "evict_alloc.hip", "page_cache_put.hip", "block_store.cpp", "cpu_codecs.cpp", "ipc.cpp", "paged_view.cpp", "ring_read.cpp", "ragged_gather.hip", "ragged_gather.cpp", "delim_index.hip", "delim_index.cpp", "field_parse.hip", "field_parse.cpp", "text_column.hip", "text_column.cpp", "text_dict.hip", "text_dict.cpp", "json_fields.hip", "json_fields.cpp", "parquet_decode.hip", "parquet_decode.cpp", "parquet_encode.hip", "parquet_encode.cpp", "parquet_stats.hip", "parquet_stats.cpp", "page_cache.cpp", "meta_codec.cpp", "fuse_server.cpp", "http_blob.cpp",
+SOURCES = ["kernels.hip", "lz4_encode.hip", "snappy_decode.hip", "evict_alloc.hip", "page_cache_put.hip", "block_store.cpp", "cpu_codecs.cpp", "ipc.cpp", "paged_view.cpp", "ring_read.cpp", "ragged_gather.hip", "ragged_gather.cpp", "delim_index.hip", "delim_index.cpp", "field_parse.hip", "field_parse.cpp", "text_column.hip", "text_column.cpp", "text_dict.hip", "text_dict.cpp", "json_fields.hip", "json_fields.cpp", "parquet_decode.hip", "parquet_decode.cpp", "parquet_encode.hip", "parquet_encode.cpp", "parquet_stats.hip", "parquet_stats.cpp", "page_cache.cpp", "meta_codec.cpp", "fuse_server.cpp", "http_blob.cpp",
            "frame_rpc.cpp", "journal_log.cpp", "sigv4.cpp", "numa_host.cpp", "data_server.cpp", "block_source.cpp", "stress_bench.cpp", "hdfs_packets.cpp", "data_path_bind.cpp", "bindings.cpp"]
-HEADERS = ["kernels.h", "block_store.h", "store_error.h", "paged_view.h", "paged_view_host.h", "cpu_codecs.h", "ipc.h", "ring_read.h", "ragged_gather.h", "delim_index.h", "delim_index_host.h", "field_parse.h", "field_parse_host.h", "text_column.h", "text_column_host.h", "text_dict.h", "text_dict_host.h", "json_fields.h", "json_fields_host.h", "json_text_host.h", "lane_group.h", "lz4_block_host.h", "parquet_decode.h", "parquet_host.h", "parquet_encode.h", "parquet_encode_host.h", "parquet_stats.h", "parquet_stats_host.h", "page_cache.h", "page_cache_bind.h", "seg_ring.h", "frame_rpc.h", "journal_log.h", "meta_codec.h", "fuse_server.h", "h2_abi.h", "data_server.h", "sigv4.h", "numa_host.h", "http_blob.h",
+HEADERS = ["kernels.h", "block_store.h", "store_error.h", "paged_view.h", "paged_view_host.h", "cpu_codecs.h", "ipc.h", "ring_read.h", "ragged_gather.h", "delim_index.h", "delim_index_host.h", "field_parse.h", "field_parse_host.h", "text_column.h", "text_column_host.h", "text_dict.h", "text_dict_host.h", "json_fields.h", "json_fields_host.h", "json_text_host.h", "lane_group.h", "lz4_block_host.h", "lz_wave.h", "snappy_host.h", "parquet_decode.h", "parquet_host.h", "parquet_encode.h", "parquet_encode_host.h", "parquet_stats.h", "parquet_stats_host.h", "page_cache.h", "page_cache_bind.h", "seg_ring.h", "frame_rpc.h", "journal_log.h", "meta_codec.h", "fuse_server.h", "h2_abi.h", "data_server.h", "sigv4.h", "numa_host.h", "http_blob.h",
            "block_source.h", "stress_bench.h", "hdfs_packets.h"]
 
 
